@@ -1,7 +1,13 @@
 """Benchmark of the hot path (BASELINE.json metric: query embeddings/sec + cosine-pairs/sec,
 100k x 768 gallery).
 
-python bench.py --gpus N --steps K --warmup W [--mode full|knn] [--preset cfg2|cfg3|cfg4|cfg5]
+python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR] [--mode full|knn]
+                [--preset cfg2|cfg3|cfg4|cfg5]
+  A plain run sets up, warms up, times the K steps and prints one JSON line (value, ms_per_step).
+  --full adds everything else to that line, measured after the timed region: the roofline object (per-GEMM
+  events, the 16-query HBM-regime kNN probes), the CPU baselines, recall / P@10 against the fp32 oracle
+  and the x3 (fp32-faithful) line.  --dump-outputs DIR writes what the last timed step returned as
+  DIR/<name>.npy (see dump_outputs).
   full (default): one step = Swin-T tower on B synthetic 224x224 images + ClinicalBERT-geometry
         tower on B synthetic 128-token reports (bf16) -> joint-embedding head (default: the
         reference's default model_type "multimodal", 5 fusion layers x 8 heads) -> exact cosine
@@ -63,7 +69,8 @@ def parse(argv=None):
                    help="run the towers and the fusion layers on one stream (for rocprof per-kernel stats; the "
                         "default overlaps the Swin tower and the patch-side fusion work on side streams)")
     p.add_argument("--no-x3-line", action="store_true",
-                   help="skip the x3 (fp32-faithful) throughput + parity block reported beside a bf16 / fp8 run")
+                   help="with --full: skip the x3 (fp32-faithful) throughput + parity block reported beside a bf16 / "
+                        "fp8 run")
     p.add_argument("--rerank", action="store_true", default=None,
                    help="fused KG / label rerank of each query's top-K candidates inside the step")
     p.add_argument("--batch", type=int, default=None)
@@ -79,7 +86,14 @@ def parse(argv=None):
     p.add_argument("--model-type", choices=["multimodal", "text", "image", "both"], default=None,
                    help="joint-embedding head: multimodal (reference default, model.py:137; 5 fusion layers, "
                         "8 heads), text / image (one tower + its head), both (both single-modality heads)")
-    p.add_argument("--no-cpu-baseline", action="store_true")
+    p.add_argument("--full", action="store_true",
+                   help="after the timed steps also measure what the headline does not need: roofline (GEMM events, "
+                        "16-query kNN probes), CPU baselines, recall / P@10 vs the fp32 oracle, the x3 line")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write the arrays the last timed step returned (query embeddings, top-K indices / scores) "
+                        "as DIR/<name>.npy")
+    p.add_argument("--no-cpu-baseline", action="store_true",
+                   help="with --full: skip the CPU baselines, the oracle recall / P@10 and the x3 line")
     p.add_argument("--collective", action="store_true",
                    help="take the sharded RCCL search path (ShardedIndex: query all-gather, packed result "
                         "all-gather, device merge) even at one rank, to time it on one GPU")
@@ -270,7 +284,7 @@ def main():
     torch.cuda.synchronize(dev)
     t0 = time.perf_counter()
     for _ in range(a.steps):
-        out = step(True)
+        out = step(a.full)  # --full: events around each search call (kNN roofline)
     torch.cuda.synchronize(dev)
     if world > 1:
         dist.barrier()
@@ -282,8 +296,93 @@ def main():
         elapsed = float(t.item())
     # every search of the timed region returned an exact list (status 0 for every query)
     check_status(st_max.view(1))
-    ms_search = sum(e0.elapsed_time(e1) for e0, e1 in ev_pairs) / max(len(ev_pairs), 1)
-    q_last, i_last, _ = out
+    q_last, i_last, s_last = out
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, q_last, i_last, s_last)
+
+    # whole-job throughput: every rank embeds B queries; every query is scored against the whole
+    # world*n gallery (each rank scores all world*B queries against its n rows)
+    nq_step = (2 * B) if (model is not None and a.model_type == "both") else B
+    q_per_s = world * nq_step * a.steps / elapsed
+    pairs_per_s = (world * nq_step) * (world * n) * a.steps / elapsed
+    Qs = world * nq_step
+
+    roof = None
+    if a.full:
+        ms_search = sum(e0.elapsed_time(e1) for e0, e1 in ev_pairs) / max(len(ev_pairs), 1)
+        lat_small, lat_cold, ms_small, nq_small = hbm_regime_probe(index, K, d, rank, dev, stream)
+        gemm_ms = {}
+        if model is not None and a.model_type != "image":
+            # per-launch GEMM timings (BERT QKV / O-proj / FFN1 / FFN2) in a short pass right after the
+            # timed region with the towers in sequence: inside the timed steps the Swin tower runs
+            # concurrently on a side stream, and events around one kernel would also count the
+            # co-running kernels' share
+            set_streams(model, False)
+            model.backbones.bert.gemm_events = {}
+            for _ in range(3):
+                step(False)
+            torch.cuda.synchronize(dev)
+            set_streams(model, not a.sequential_towers)
+            for name, evs in model.backbones.bert.gemm_events.items():
+                gemm_ms[name] = sum(e0.elapsed_time(e1) for e0, e1 in evs) / max(len(evs), 1)
+            model.backbones.bert.gemm_events = None
+        ln_fold = bool(model is not None and a.model_type != "image"
+                       and getattr(model.backbones.bert, "ln_fold", False) and (B * 128) % 256 == 0)
+        roof, _ = roofline(a, n, d, K, Qs, ms_search, ms_small, nq_small, gemm_ms, B, lat_small, lat_cold,
+                           ln_fold=ln_fold)
+
+    cpu = cpu_knn = recall = p10 = x3_line = None
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline:
+        if model is None:
+            cpu = cpu_baseline_knn(a, G, qbatch.cpu().numpy())
+        else:
+            cpu, emb_cpu = cpu_baseline_full(a, G, imgs, ids, mask)
+            cpu_knn = cpu_baseline_knn(a, G, q_last[:64].cpu().numpy())
+            nq_par = min(a.parity_queries, q_last.shape[0] if a.model_type != "both" else B)
+            emb_par = oracle_embeddings(a, imgs, ids, mask, nq_par)
+            q_par = q_last[:nq_par] if a.model_type != "both" else torch.cat([q_last[:nq_par], q_last[B:B + nq_par]])
+            recall = recall_vs_cpu(index, q_par, emb_par, G, K)
+            p10 = precision_vs_cpu(q_par, emb_par, d, a.knn_mode)
+            del emb_cpu
+            if a.tower_dtype != "x3" and not a.no_x3_line and a.model_type in ("multimodal", "text") and B <= 2048:
+                x3_line = x3_block(a, index, G, imgs, ids, mask, emb_par, nq_par, K, dev, steps=10 if B <= 1024 else 3)
+
+    if rank == 0:
+        print(json.dumps(result_line(a, world, coll, n, d, K, B, elapsed, q_per_s, pairs_per_s, roof, recall, p10,
+                                     cpu, cpu_knn, x3_line)), flush=True)
+    if coll:
+        dist.destroy_process_group()
+
+
+DUMP_MAX_BYTES = 16 << 20  # per array (three arrays: well under 64 MB in all)
+
+
+def dump_outputs(out_dir, q, idx, scores):
+    """--dump-outputs: what the last timed step returned to its caller, as <out_dir>/<name>.npy:
+    query_embeddings (nq, d) float32, topk_indices (nq, K) float64 (global gallery row ids, exact in
+    f64), topk_scores (nq, K) float32 (absent where the path returns none: the sharded rerank).  The
+    inputs are seeded, so two builds run with the same arguments are comparable array for array.  An
+    array past DUMP_MAX_BYTES is cut to a fixed seeded sample of its rows (sorted row numbers)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"query_embeddings": (q, np.float32), "topk_indices": (idx, np.float64), "topk_scores": (scores, np.float32)}
+    for name, (t, dt) in arrays.items():
+        if t is None:
+            continue
+        x = np.ascontiguousarray(t.detach().cpu().numpy().astype(dt))
+        rows = max(1, DUMP_MAX_BYTES // max(1, x[0].nbytes))
+        if x.shape[0] > rows:
+            keep = np.sort(np.random.default_rng(20260).choice(x.shape[0], size=rows, replace=False))
+            x = x[keep]
+        np.save(os.path.join(out_dir, name + ".npy"), x)
+
+
+def hbm_regime_probe(index, K, d, rank, dev, stream):
+    """--full: 16-query searches after the timed region.  Returns (single-search latency ms, the same
+    with the Infinity Cache flushed, ms per search of 20 back to back, the query count)."""
+    import torch
+    from mmr_amd import synthetic
+    from mmr_amd.retrieval import check_status
     # HBM-bound regime probe (after the timed region): 16 resident queries — the f16 scan's one-tile
     # stream (knn_scan_f16_gmax<1>) or, in x3 mode, the skinny f32 stream — timed with events on the
     # launch stream, whole search call
@@ -336,91 +435,51 @@ def main():
     for st16 in sts:
         check_status(st16)
     ms_small = e0.elapsed_time(e1) / NB
-    gemm_ms = {}
-    if model is not None and a.model_type != "image":
-        # per-launch GEMM timings (BERT QKV / O-proj / FFN1 / FFN2) in a short pass right after the
-        # timed region with the towers in sequence: inside the timed steps the Swin tower runs
-        # concurrently on a side stream, and events around one kernel would also count the
-        # co-running kernels' share
-        set_streams(model, False)
-        model.backbones.bert.gemm_events = {}
-        for _ in range(3):
-            step(False)
-        torch.cuda.synchronize(dev)
-        set_streams(model, not a.sequential_towers)
-        for name, evs in model.backbones.bert.gemm_events.items():
-            gemm_ms[name] = sum(e0.elapsed_time(e1) for e0, e1 in evs) / max(len(evs), 1)
-        model.backbones.bert.gemm_events = None
+    return lat_small, lat_cold, ms_small, q16.shape[0]
 
-    # whole-job throughput: every rank embeds B queries; every query is scored against the whole
-    # world*n gallery (each rank scores all world*B queries against its n rows)
-    nq_step = (2 * B) if (model is not None and a.model_type == "both") else B
-    q_per_s = world * nq_step * a.steps / elapsed
-    pairs_per_s = (world * nq_step) * (world * n) * a.steps / elapsed
-    Qs = world * nq_step
-    ln_fold = bool(model is not None and a.model_type != "image" and getattr(model.backbones.bert, "ln_fold", False)
-                   and (B * 128) % 256 == 0)
-    roof, knn_roof = roofline(a, n, d, K, Qs, ms_search, ms_small, q16.shape[0], gemm_ms, B, lat_small, lat_cold,
-                              ln_fold=ln_fold)
 
-    cpu = cpu_knn = recall = p10 = x3_line = None
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
-        if model is None:
-            cpu = cpu_baseline_knn(a, G, qbatch.cpu().numpy())
-        else:
-            cpu, emb_cpu = cpu_baseline_full(a, G, imgs, ids, mask)
-            cpu_knn = cpu_baseline_knn(a, G, q_last[:64].cpu().numpy())
-            nq_par = min(a.parity_queries, q_last.shape[0] if a.model_type != "both" else B)
-            emb_par = oracle_embeddings(a, imgs, ids, mask, nq_par)
-            q_par = q_last[:nq_par] if a.model_type != "both" else torch.cat([q_last[:nq_par], q_last[B:B + nq_par]])
-            recall = recall_vs_cpu(index, q_par, emb_par, G, K)
-            p10 = precision_vs_cpu(q_par, emb_par, d, a.knn_mode)
-            del emb_cpu
-            if a.tower_dtype != "x3" and not a.no_x3_line and a.model_type in ("multimodal", "text") and B <= 2048:
-                x3_line = x3_block(a, index, G, imgs, ids, mask, emb_par, nq_par, K, dev, steps=10 if B <= 1024 else 3)
-
-    if rank == 0:
-        workload = {
-            "multimodal": "Swin-T + BERT-base towers + 5-layer multimodal fusion head",
-            "text": "text-only BERT-base tower + text head", "image": "Swin-T tower + image head",
-            "both": "Swin-T + BERT-base towers + image and text heads"}[a.model_type]
-        line = {
-            "metric": "query embeddings/sec + cosine-pairs/sec @ Recall@10, 100k x 768 gallery",
-            "value": q_per_s if a.mode == "full" else pairs_per_s,
-            "unit": "query_embeddings/s" if a.mode == "full" else "cosine_pairs/s",
-            "cosine_pairs_per_s": pairs_per_s,
-            "query_embeddings_per_s": q_per_s if a.mode == "full" else None,
-            "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
-            "ms_per_step": elapsed / a.steps * 1e3,
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": ({"fp8": "MX-fp8 (e4m3 + E8M0/32) tower linears, bf16 elsewhere / ",
-                       "x3": "f32 towers (every contraction bf16x3 MFMA, f32 accumulate) / "}.get(a.tower_dtype, "bf16 towers / ")
-                      if a.mode == "full" else "") + (
-                "fp16 gallery (native fp16 index: the raw rows are the scan operand), exact f64 re-rank"
-                if a.gallery_dtype == "fp16" else
-                "f32 gallery, fp16 unit-row scan copy, exact f64 re-rank" if a.knn_mode == "f16"
-                else "f32 gallery, bf16x3 scan, exact f64 re-rank"),
-            "data": "synthetic (seeded N(0,1) gallery; random-init weights)",
-            "config": {"workload": ("%s: %s%s, B=%d, top-%d over %dx%d %s per GPU%s" % (
-                a.preset, workload, " (MX-fp8 BERT + Swin stage 3-4 linears)" if a.tower_dtype == "fp8" else "", B, K, n, d,
-                "fp16" if a.gallery_dtype == "fp16" else "f32",
-                " + fused KG/label rerank of the %d candidates" % K if a.rerank else ""))
-                       if a.mode == "full" else ("%s kNN only: Q=%d, top-%d over %dx%d f32 per GPU" % (a.preset, B, K, n, d)),
-                       "global_batch": world * B, "gallery_rows": world * n, "dim": d, "k": K,
-                       "parallelism": (f"gallery row-shard x{world} + tower DP x{world}" if world > 1 else
-                                       "single rank, sharded RCCL search path (--collective)" if coll else "single")},
-            "roofline": roof,
-            "knn_status_ok": True,
-            "recall_at_10_vs_cpu": recall["recall_at_k"] if recall else None,
-            "recall_vs_cpu": recall,
-            "p_at_10": p10,
-            "cpu_baseline": cpu,
-            "cpu_baseline_knn": cpu_knn,
-            "x3_mode": x3_line,
-        }
-        print(json.dumps(line), flush=True)
-    if coll:
-        dist.destroy_process_group()
+def result_line(a, world, coll, n, d, K, B, elapsed, q_per_s, pairs_per_s, roof, recall, p10, cpu, cpu_knn, x3_line):
+    """The JSON result line.  roofline, recall / P@10, the CPU baselines and the x3 line are measured
+    under --full only (null in a plain run)."""
+    workload = {
+        "multimodal": "Swin-T + BERT-base towers + 5-layer multimodal fusion head",
+        "text": "text-only BERT-base tower + text head", "image": "Swin-T tower + image head",
+        "both": "Swin-T + BERT-base towers + image and text heads"}[a.model_type]
+    line = {
+        "metric": "query embeddings/sec + cosine-pairs/sec @ Recall@10, 100k x 768 gallery",
+        "value": q_per_s if a.mode == "full" else pairs_per_s,
+        "unit": "query_embeddings/s" if a.mode == "full" else "cosine_pairs/s",
+        "cosine_pairs_per_s": pairs_per_s,
+        "query_embeddings_per_s": q_per_s if a.mode == "full" else None,
+        "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
+        "ms_per_step": elapsed / a.steps * 1e3,
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": ({"fp8": "MX-fp8 (e4m3 + E8M0/32) tower linears, bf16 elsewhere / ",
+                   "x3": "f32 towers (every contraction bf16x3 MFMA, f32 accumulate) / "}.get(a.tower_dtype, "bf16 towers / ")
+                  if a.mode == "full" else "") + (
+            "fp16 gallery (native fp16 index: the raw rows are the scan operand), exact f64 re-rank"
+            if a.gallery_dtype == "fp16" else
+            "f32 gallery, fp16 unit-row scan copy, exact f64 re-rank" if a.knn_mode == "f16"
+            else "f32 gallery, bf16x3 scan, exact f64 re-rank"),
+        "data": "synthetic (seeded N(0,1) gallery; random-init weights)",
+        "config": {"workload": ("%s: %s%s, B=%d, top-%d over %dx%d %s per GPU%s" % (
+            a.preset, workload, " (MX-fp8 BERT + Swin stage 3-4 linears)" if a.tower_dtype == "fp8" else "", B, K, n, d,
+            "fp16" if a.gallery_dtype == "fp16" else "f32",
+            " + fused KG/label rerank of the %d candidates" % K if a.rerank else ""))
+                   if a.mode == "full" else ("%s kNN only: Q=%d, top-%d over %dx%d f32 per GPU" % (a.preset, B, K, n, d)),
+                   "global_batch": world * B, "gallery_rows": world * n, "dim": d, "k": K,
+                   "parallelism": (f"gallery row-shard x{world} + tower DP x{world}" if world > 1 else
+                                   "single rank, sharded RCCL search path (--collective)" if coll else "single")},
+        "roofline": roof,
+        "knn_status_ok": True,
+        "recall_at_10_vs_cpu": recall["recall_at_k"] if recall else None,
+        "recall_vs_cpu": recall,
+        "p_at_10": p10,
+        "cpu_baseline": cpu,
+        "cpu_baseline_knn": cpu_knn,
+        "x3_mode": x3_line,
+    }
+    return line
 
 
 def set_streams(model, on):

@@ -18,34 +18,34 @@ for s in $STEPS; do
       timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $OUT/smoke.log 2>&1
       tail -1 $OUT/smoke.log ;;
     bench)
-      timeout -k 10 300 python -u bench.py > $OUT/bench_full.json 2> $OUT/bench_full.err
-      timeout -k 10 300 python -u bench.py --mode knn > $OUT/bench_knn.json 2> $OUT/bench_knn.err
+      timeout -k 10 300 python -u bench.py --full > $OUT/bench_full.json 2> $OUT/bench_full.err
+      timeout -k 10 300 python -u bench.py --full --mode knn > $OUT/bench_knn.json 2> $OUT/bench_knn.err
       echo bench ok ;;
     presets)
-      timeout -k 10 900 python -u bench.py --preset cfg3 --steps 5 --warmup 2 > $OUT/bench_cfg3.json 2> $OUT/bench_cfg3.err
-      timeout -k 10 800 python -u bench.py --preset cfg5 --steps 5 --warmup 2 > $OUT/bench_cfg5.json 2> $OUT/bench_cfg5.err
+      timeout -k 10 900 python -u bench.py --full --preset cfg3 --steps 5 --warmup 2 > $OUT/bench_cfg3.json 2> $OUT/bench_cfg3.err
+      timeout -k 10 800 python -u bench.py --full --preset cfg5 --steps 5 --warmup 2 > $OUT/bench_cfg5.json 2> $OUT/bench_cfg5.err
       echo presets ok ;;
     cfg3)  # closing cfg3 record: cpu_baseline, recall_vs_cpu, p_at_10 and the x3 parity line filled in
-      timeout -k 10 900 python -u bench.py --preset cfg3 --steps 5 --warmup 2 > $OUT/bench_cfg3.json 2> $OUT/bench_cfg3.err
+      timeout -k 10 900 python -u bench.py --full --preset cfg3 --steps 5 --warmup 2 > $OUT/bench_cfg3.json 2> $OUT/bench_cfg3.err
       echo cfg3 ok ;;
     cfg5)
-      timeout -k 10 800 python -u bench.py --preset cfg5 --steps 5 --warmup 2 > $OUT/bench_cfg5.json 2> $OUT/bench_cfg5.err
+      timeout -k 10 800 python -u bench.py --full --preset cfg5 --steps 5 --warmup 2 > $OUT/bench_cfg5.json 2> $OUT/bench_cfg5.err
       echo cfg5 ok ;;
     prof)
       timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -o full \
-        -- python3 bench.py --sequential-towers --steps 10 --warmup 2 --no-cpu-baseline > $OUT/prof_full.log 2>&1
+        -- python3 bench.py --full --sequential-towers --steps 10 --warmup 2 --no-cpu-baseline > $OUT/prof_full.log 2>&1
       timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -o knn \
-        -- python3 bench.py --sequential-towers --mode knn --steps 20 --warmup 3 --no-cpu-baseline > $OUT/prof_knn.log 2>&1
+        -- python3 bench.py --full --sequential-towers --mode knn --steps 20 --warmup 3 --no-cpu-baseline > $OUT/prof_knn.log 2>&1
       echo prof ok ;;
     prof5)  # cfg5 kernel stats, towers / fusion in sequence
       timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -o cfg5 \
-        -- python3 bench.py --sequential-towers --preset cfg5 --steps 3 --warmup 2 --no-cpu-baseline > $OUT/prof_cfg5.log 2>&1
+        -- python3 bench.py --full --sequential-towers --preset cfg5 --steps 3 --warmup 2 --no-cpu-baseline > $OUT/prof_cfg5.log 2>&1
       echo prof5 ok ;;
     pmck)
       timeout -s KILL 120 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/pmc -o kfetch \
-        -- python3 bench.py --sequential-towers --mode knn --steps 5 --warmup 1 --no-cpu-baseline > $OUT/pmc_kfetch.log 2>&1
+        -- python3 bench.py --full --sequential-towers --mode knn --steps 5 --warmup 1 --no-cpu-baseline > $OUT/pmc_kfetch.log 2>&1
       timeout -s KILL 120 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $OUT/pmc -o kwrite \
-        -- python3 bench.py --sequential-towers --mode knn --steps 5 --warmup 1 --no-cpu-baseline > $OUT/pmc_kwrite.log 2>&1
+        -- python3 bench.py --full --sequential-towers --mode knn --steps 5 --warmup 1 --no-cpu-baseline > $OUT/pmc_kwrite.log 2>&1
       echo pmc ok ;;
     pmcx3)  # x3 kernels' counters (tools/pmc_x3.py) -> gpurun_out/pmc_<tag>/pmc_x3.json
       bash tools/gpu_pmc_x3.sh $TAG > $OUT/pmc_x3.log 2>&1 || { tail -5 $OUT/pmc_x3.log; exit 1; }

@@ -1,13 +1,16 @@
 """Per-kernel register / spill / LDS summary from hipcc -Rpass-analysis=kernel-resource-usage.
 usage: python tools/kres.py <file.hip> [name filter]"""
+import os
 import re
 import subprocess
 import sys
 
 src = sys.argv[1]
 flt = sys.argv[2] if len(sys.argv) > 2 else ""
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 out = subprocess.run(["/opt/rocm/bin/hipcc", "-x", "hip", "--offload-arch=gfx950", "-O3", "-std=c++17",
-                      "-I/root/repo/include", "-I/root/repo/multi-modal-retrieval-predict-project_amd/csrc", "-c", src, "-o", "/dev/null",
+                      "-I" + os.path.join(ROOT, "include"),
+                      "-I" + os.path.join(ROOT, "multi-modal-retrieval-predict-project_amd", "csrc"), "-c", src, "-o", "/dev/null",
                       "-Rpass-analysis=kernel-resource-usage"], capture_output=True, text=True).stderr
 cur = None
 rows = {}
