@@ -447,6 +447,16 @@ mmr_status mmr_mha(const uint16_t* q, int64_t ldq, const uint16_t* k, int64_t ld
 mmr_status mmr_mha_q8(const uint16_t* q, int64_t ldq, const uint16_t* k, int64_t ldk, const uint16_t* v, int64_t ldv,
                       uint16_t* out, int64_t ldo, float* mean_out, uint8_t* q8, uint8_t* q8_scales, int32_t b,
                       int32_t lq, int32_t lk, int32_t heads, int32_t dh, float scale, void* stream);
+/* The attention weights nn.MultiheadAttention returns beside its output with its defaults (need_weights,
+ * average_attn_weights; eval, no masks): probs[bi*lq + i][c] = (1 / heads) sum_h softmax_c(q_h[i] . k_h[c] * scale),
+ * f32 — the reference's return_attention maps (src/Model/fusion.py:427,433, model.py:399).  q / k rows as
+ * mmr_mha (bf16; one bf16 MFMA product per q.k, exact in f32), softmax and head average in f32; output row
+ * (bi*lq + i) at probs + row*ldp, columns [0, lk) written, columns lk..ldp untouched (ldp >= lk, any
+ * alignment of the rows).  dh % 8 == 0, dh <= 192; q / k strides multiples of 8 elements; any lq / lk >= 1
+ * (keys stream from global memory: no bound on lk); heads <= 223 (per-head softmax statistics live in LDS;
+ * MMR_ERR_UNSUPPORTED beyond).  No atomics, fixed head order: bitwise deterministic.  b == 0: no launch. */
+mmr_status mmr_mha_probs(const uint16_t* q, int64_t ldq, const uint16_t* k, int64_t ldk, float* probs, int64_t ldp,
+                         int32_t b, int32_t lq, int32_t lk, int32_t heads, int32_t dh, float scale, void* stream);
 
 /* y = x + pos[row % l] -> bf16 (rows, c); x f32 (x_is_f32) or bf16; pos f32 [>= l][c]
  * (PreFusionEnhancer.pos_embed fusion.py:32). c % 8 == 0. */
@@ -530,6 +540,12 @@ mmr_status mmr_x3_linear_p8(const uint16_t* xs, const uint16_t* w2, const float*
 mmr_status mmr_x3_attention(const float* q, int64_t ldq, const float* k, int64_t ldk, const float* v, int64_t ldv,
                             float* out, int64_t ldo, float* mean_out, const int64_t* mask01, int32_t b, int32_t lq,
                             int32_t lk, int32_t heads, int32_t dh, float scale, void* stream);
+/* mmr_mha_probs on f32 rows (the x3 mode's attention maps): q and k split hi / lo in registers and each
+ * q.k summed as hi.hi + hi.lo + lo.hi, exactly as mmr_x3_attention's scores; softmax (mmr::exp_acc) and head
+ * average in f32.  dh % 8 == 0, dh <= 128; strides multiples of 4 elements. */
+mmr_status mmr_x3_attention_probs(const float* q, int64_t ldq, const float* k, int64_t ldk, float* probs, int64_t ldp,
+                                  int32_t b, int32_t lq, int32_t lk, int32_t heads, int32_t dh, float scale,
+                                  void* stream);
 /* Swin (shifted-)window attention as mmr_swin_window_attention on f32 qkv (b*hw*hw, 3c) -> out
  * (b*hw*hw, c), q scaled by dh^-0.5 before q k^T (timm), bias from mmr_swin_attn_bias.  head_dim <= 32. */
 mmr_status mmr_x3_swin_window_attention(const float* qkv, const float* bias, float* out, int32_t b, int32_t hw,

@@ -23,6 +23,10 @@ Every fusion layer reads the SAME backbone features (img_global, img_patches, tx
                    bf16x3 MFMA: ops.linear_x3, ~2^-17 relative per product; exact f32 with
                    exact_query_linears=True)
 
+  attention maps   forward(..., return_attention=True) only: the head-averaged softmax weights of the two
+                   cross attentions and the combiner (model.py:399-420), by ops.mha_probs /
+                   x3_attention_probs on the same q / k rows — the attention cores never hold P
+
 bf16 activations / f32 accumulation for the token-level work, f32 for every per-query vector (its
 linears on bf16x3 MFMA).
 tower_dtype="fp8" (BASELINE config 5): the token-level GEMMs — each enhancer's in_proj and out_proj,
@@ -302,10 +306,16 @@ class FusionStack:
             t.record_stream(main)
         return w["pq"], w["pp"], w["ev"], True
 
-    def forward(self, img_global, img_patches, txt_feats, patch_work=None):
+    def forward(self, img_global, img_patches, txt_feats, patch_work=None, return_attention=False):
         """img_global (B, Ci) f32, img_patches (B, Np, Ci) f32, txt_feats (B, L, Ct) bf16/f32 or None
         -> joint_emb (B, D) f32.  patch_work: this batch's patch_work(img_patches), started early by the
         caller (else it runs here).
+
+        return_attention: -> (joint_emb, attn), attn the reference's head-averaged attention maps as device
+        f32 tensors, per layer i "layer_{i}_comb" (B, Np+2, Np+2), "layer_{i}_txt2img" (B, L, Np) and
+        "layer_{i}_img2txt" (B, Np, L) (model.py:399-420; L = 1 for the default text token).  They come from
+        extra launches (ops.mha_probs / x3_attention_probs) on the q / k rows the attention cores read; the
+        value path runs the same launches on the same operands, so joint_emb has the same bits either way.
 
         Phase 1 (per layer, token level): enhancers, folded cross projections, the two cross
         attentions (means only where only means are used), patches_fused.
@@ -315,7 +325,7 @@ class FusionStack:
         nl*B*(Np+2) rows, its attention means and out-projection.
         Phase 4 (sequential): the joint chain (norm1 / alpha, norm2 -> FFN, adapter)."""
         if self.x3:
-            return self._forward_x3(img_global, img_patches, txt_feats, patch_work)
+            return self._forward_x3(img_global, img_patches, txt_feats, patch_work, return_attention)
         B, Np, Ci = img_patches.shape
         D, h, eps, dev = self.D, self.heads, self.eps, self.device
         nl = len(self.layers)
@@ -326,6 +336,7 @@ class FusionStack:
         m2 = torch.empty((nl, B, D), dtype=torch.float32, device=dev)
         PF = torch.empty((nl, B * Np, D), dtype=torch.bfloat16, device=dev)
         cls = None
+        attn = {} if return_attention else None
         # the patch-side token work of every layer depends only on the image tower: it runs on a side
         # stream (or the caller's early patch_work), ahead of and concurrently with the text-side work,
         # which waits per layer on an event before the cross attentions (side_streams = False: one
@@ -354,6 +365,9 @@ class FusionStack:
             if two:
                 main.wait_event(ev[i])
             PQ, PP = pq[i], pp[i]
+            if attn is not None:  # on the main stream, after the wait: PQ is ready (and recorded on main)
+                attn[f"layer_{i}_txt2img"] = ops.mha_probs(TQ[:, :D], PQ[:, :D], B, Lt, Np, h, dh, sc)
+                attn[f"layer_{i}_img2txt"] = ops.mha_probs(PQ[:, 2 * D:], TQ[:, D:2 * D], B, Np, Lt, h, dh, sc)
             ops.mha(TQ[:, :D], PQ[:, :D], PQ[:, D:2 * D], B, Lt, Np, h, dh, sc, mean_out=m1[i])
             if self.fp8 and (B * Np) % 256 == 0 and D % 256 == 0 and dh % 32 == 0:  # the attention core emits the o2 operand
                 _, _, a28 = ops.mha(PQ[:, 2 * D:], TQ[:, D:2 * D], TQ[:, 2 * D:], B, Np, Lt, h, dh, sc, mean_out=m2[i],
@@ -364,9 +378,9 @@ class FusionStack:
                 ops.mha(PQ[:, 2 * D:], TQ[:, D:2 * D], TQ[:, 2 * D:], B, Np, Lt, h, dh, sc, out=a2, mean_out=m2[i])
                 ops.linear(a2, L["o2_wb"], L["o2_b"], residual=PP, out=PF[i])  # patches_fused (fusion.py:437)
         del pq, pp
-        return self._finish(G, m1, m2, cls, PF, B, Np, Ci)
+        return self._finish(G, m1, m2, cls, PF, B, Np, Ci, attn)
 
-    def _forward_x3(self, img_global, img_patches, txt_feats, patch_work=None):
+    def _forward_x3(self, img_global, img_patches, txt_feats, patch_work=None, return_attention=False):
         """Phase 1 of forward in the fp32-faithful mode: f32 token rows, every GEMM and attention on
         bf16x3 (ops.x3_linear / ops.x3_attention).  As in the bf16 path, the patch-side work of every
         layer (enhancer, folded k/v/q + patch projections) runs on a side stream (or early, by the
@@ -384,6 +398,7 @@ class FusionStack:
         main = torch.cuda.current_stream(dev)
         pq, pp, ev, two = self._patch_side(img_patches, patch_work)
         cls = torch.empty((nl, B, self.layers[0]["txt"].C), dtype=torch.float32, device=dev)
+        attn = {} if return_attention else None
         for i, L in enumerate(self.layers):
             PQ, PP = pq[i], pp[i]
             if txt_feats is None:  # learnable default text token (fusion.py:404-407)
@@ -397,15 +412,19 @@ class FusionStack:
             TQ = ops.x3_linear(Tes, L["t_x3"], L["t_b"]).reshape(B * Lt, -1)  # q_t2i | k_i2t | v_i2t
             if two:
                 main.wait_event(ev[i])
+            if attn is not None:
+                attn[f"layer_{i}_txt2img"] = ops.x3_attention_probs(TQ[:, :D], PQ[:, :D], B, Lt, Np, h, dh, sc)
+                attn[f"layer_{i}_img2txt"] = ops.x3_attention_probs(PQ[:, 2 * D:], TQ[:, D:2 * D], B, Np, Lt, h, dh, sc)
             ops.x3_attention(TQ[:, :D], PQ[:, :D], PQ[:, D:2 * D], B, Lt, Np, h, dh, sc, mean_out=m1[i])
             a2 = ops.x3_attention_split(PQ[:, 2 * D:], TQ[:, D:2 * D], TQ[:, 2 * D:], B, Np, Lt, h, dh, sc,
                                         mean_out=m2[i])
             ops.x3_linear(a2, L["o2_x3t"], L["o2_b"], residual=PP, out=PF[i])  # patches_fused (fusion.py:437)
         del pq, pp
-        return self._finish(G, m1, m2, cls, PF, B, Np, Ci)
+        return self._finish(G, m1, m2, cls, PF, B, Np, Ci, attn)
 
-    def _finish(self, G, m1, m2, cls, PF, B, Np, Ci):
-        """Phases 2-4 of forward (shared by the bf16 / fp8 and x3 modes)."""
+    def _finish(self, G, m1, m2, cls, PF, B, Np, Ci, attn=None):
+        """Phases 2-4 of forward (shared by the bf16 / fp8 and x3 modes).  attn: the cross-attention maps of
+        phase 1 (return_attention) — the combiner's maps are added and (joint, attn) returned."""
         D, h, eps, dev = self.D, self.heads, self.eps, self.device
         nl = len(self.layers)
         dh = D // h
@@ -433,6 +452,11 @@ class FusionStack:
             SQ = ops.linear(S, self.s_w, self.s_b)
         if not self.x3:
             ops.mha(SQ[:, :D], SQ[:, D:2 * D], SQ[:, 2 * D:], nl * B, Np + 2, Np + 2, h, dh, sc, mean_out=m3)
+        if attn is not None:  # rows [i B, (i + 1) B) of the launch over the nl*B sequences are layer i's
+            probs = ops.x3_attention_probs if self.x3 else ops.mha_probs
+            comb = probs(SQ[:, :D], SQ[:, D:2 * D], nl * B, Np + 2, Np + 2, h, dh, sc)
+            attn = {f"layer_{i}_{k}": comb[i * B:(i + 1) * B] if k == "comb" else attn[f"layer_{i}_{k}"]
+                    for i in range(nl) for k in ("comb", "txt2img", "img2txt")}  # the reference's key order
         fused = self._ql(m3, self.s_ow_x3, self.s_ob).view(nl, B, D)  # mean of self_attn output
         # phase 4: the joint chain
         joint = None
@@ -449,4 +473,4 @@ class FusionStack:
             a1, a2 = L["ad_x3"]
             self._ql(self._ql(x, a1, c1, act=1), a2, c2, residual=x, out=x)
             joint = x
-        return joint.contiguous()
+        return joint.contiguous() if attn is None else (joint.contiguous(), attn)

@@ -15,7 +15,9 @@ MultiModalRetrievalModel.forward(...) -> {"joint_emb", "img_emb", "txt_emb", "lo
     use_shared_ffn (reference default True, configs/config.yaml false).
     "multimodal" = num_fusion_layers x CrossModalFusion (fusion.py:334-471) + combiner
     (model.py:375-459) on libmmr kernels (mmr_amd/fusion.py); the classifier (logits) is
-    classification, out of scope -> None; attention maps (return_attention) are not produced.
+    classification, out of scope -> None; return_attention=True fills "attn" with the reference's
+    head-averaged maps layer_{i}_comb / _txt2img / _img2txt (model.py:399-420, CPU f32 tensors; {} for
+    the image / text heads, None without the flag).
 """
 import collections
 import json
@@ -340,13 +342,17 @@ class MultiModalRetrievalModel:
             txt_mean = self._txt_pool(txt)
         img_emb = ops.proj_head(img_global, *self.img_proj) if img_global is not None else None
         txt_emb = ops.proj_head(txt_mean, *self.txt_proj) if txt_mean is not None else None
-        if mm:
+        attn = {} if return_attention else None  # model.py:345,488: the image / text heads leave it empty
+        if mm and return_attention:
+            joint, maps = self.fusion.forward(img_global, patches, txt, return_attention=True)
+            attn = {k: v.detach().cpu() for k, v in maps.items()}  # model.py:404-420
+        elif mm:
             joint = self.fusion.forward(img_global, patches, txt)
         elif self.model_type == "image":
             joint = self._head(pool, self.img_proj)
         else:
             joint = self._head(txt_mean, self.txt_proj)
-        return {"joint_emb": joint, "img_emb": img_emb, "txt_emb": txt_emb, "logits": None, "attn": None}
+        return {"joint_emb": joint, "img_emb": img_emb, "txt_emb": txt_emb, "logits": None, "attn": attn}
 
     __call__ = forward
 

@@ -498,6 +498,27 @@ def mha(q, k, v, b, lq, lk, heads, dh, scale, out=None, mean_out=None, q8=False)
     return out, mean_out
 
 
+def _probs(fn, name, q, k, b, lq, lk, heads, dh, scale, out):
+    _lib.require_gpu(q)
+    if out is None:
+        out = torch.empty((b, lq, lk), dtype=torch.float32, device=q.device)
+    _chk(fn(_lib.ptr(q), q.stride(0), _lib.ptr(k), k.stride(0), _lib.ptr(out), out.stride(-2), b, lq, lk, heads, dh,
+            float(scale), _s(q)), name)
+    return out
+
+
+def mha_probs(q, k, b, lq, lk, heads, dh, scale, out=None):
+    """Head-averaged attention probabilities of mha's q / k (strided bf16 row views): (b, lq, lk) f32 =
+    mean_h softmax(q_h k_h^T * scale), nn.MultiheadAttention's returned weights.  out: f32, rows of
+    >= lk floats at stride out.stride(-2) (columns past lk are left untouched)."""
+    return _probs(_L().mmr_mha_probs, "mmr_mha_probs", q, k, b, lq, lk, heads, dh, scale, out)
+
+
+def x3_attention_probs(q, k, b, lq, lk, heads, dh, scale, out=None):
+    """mha_probs on f32 rows, the scores on bf16x3 as x3_attention's (mmr_x3_attention_probs)."""
+    return _probs(_L().mmr_x3_attention_probs, "mmr_x3_attention_probs", q, k, b, lq, lk, heads, dh, scale, out)
+
+
 def add_pos(x, pos, l, q8=False):
     """bf16 (rows, c) = x + pos[row % l] for x (..., c) f32 or bf16 contiguous, pos f32 [>= l][c].
     q8: also its MX-fp8 activation operand, returned as (y, MXFP8) (rows % 256 == 0, C % 256 == 0)."""
