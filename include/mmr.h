@@ -317,7 +317,10 @@ mmr_status mmr_bert_embed_q8(const int64_t* ids, const float* word, const float*
 
 /* BERT self-attention core (HF BertSelfAttention, eval): qkv bf16 (b*l, 3*h*dh) [q|k|v],
  * additive mask from mask01 (b, l) int64 (0 -> masked), softmax(q k^T / sqrt(dh)) v -> ctx bf16
- * (b*l, h*dh).  Any l; dh % 8 == 0, dh <= 192 (the mmr_mha kernel with a key mask). */
+ * (b*l, h*dh).  Any l; dh % 8 == 0, dh <= 192 (the mmr_mha kernel with a key mask).
+ * A sequence whose mask01 row is all zero follows HF: finfo.min is added to every score, the softmax
+ * is uniform, and every context row of that sequence is the mean of V over its l keys (finite, never
+ * NaN; mmr_x3_attention does the same).  Sequences with at least one live key are unaffected. */
 mmr_status mmr_bert_attention(const uint16_t* qkv, const int64_t* mask01, uint16_t* ctx,
                               int32_t b, int32_t l, int32_t h, int32_t dh, void* stream);
 

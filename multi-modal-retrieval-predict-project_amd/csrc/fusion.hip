@@ -246,7 +246,36 @@ __global__ __launch_bounds__(256, DT == 1 ? 4 : (DT <= 3 ? 3 : 2)) void mha_smal
   float* red = (float*)smem + wave * DHP * RLD;
   __syncthreads();
   if (active) {
-    const float inv = 1.0f / (l_run + __shfl_xor(l_run, 32, 64));
+    float l_sum = l_run + __shfl_xor(l_run, 32, 64);
+    if constexpr (MASK) {
+      // A sequence whose keys are ALL masked: HF adds finfo.min to every scaled score, all of them round to
+      // finfo.min and the softmax is uniform, so the context is the mean of V over the lk keys (x3_mha's
+      // anyv).  Here tile 0 is then the only tile kept, every score in it is exactly -FLT_MAX = m_run, and
+      // p = exp2(fma(s, c2, -fl(m c2))) is 2^-(rounding error of FLT_MAX c2) = 0 for every key: l = 0 and
+      // O = 0 * inf.  Block-uniform (the mask is per key), and never taken with a live key (m_run is then
+      // a real score), so every other sequence keeps its bits.  Cold path: V straight from global memory,
+      // 8 B per (key, 4 channels of this lane's O registers), f32 sum in key order.
+      if (m_run == -FLT_MAX) {
+#pragma unroll
+        for (int dt = 0; dt < DT; ++dt) o[dt] = (f32x16){0};
+        for (int key = 0; key < lk; ++key) {
+          const uint16_t* vrow = vbase + (int64_t)key * ldv + 4 * hf;
+#pragma unroll
+          for (int dt = 0; dt < DT; ++dt)
+#pragma unroll
+            for (int g4 = 0; g4 < 4; ++g4) {
+              const int d = dt * 32 + 8 * g4;  // + 4 hf + 0..3: inside dh as a whole (dh % 8 == 0)
+              if (d < dh) {
+                const bf16x4 u = *(const bf16x4*)(vrow + d);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) o[dt][4 * g4 + e] += bf2f((uint16_t)u[e]);
+              }
+            }
+        }
+        l_sum = (float)lk;
+      }
+    }
+    const float inv = 1.0f / l_sum;
     if (out != nullptr || q8 != nullptr) {
       uint16_t* st = (uint16_t*)red;
 #pragma unroll
@@ -814,7 +843,8 @@ mmr_status mmr_mha(const uint16_t* q, int64_t ldq, const uint16_t* k, int64_t ld
 }
 
 // BERT self-attention (HF BertSelfAttention, eval) on the same kernel: Q / K / V are the column
-// blocks of the fused QKV rows; key padding mask01 (0 -> masked; fully masked 32-key tiles skipped)
+// blocks of the fused QKV rows; key padding mask01 (0 -> masked; fully masked 32-key tiles skipped).
+// A sequence with every key masked gets HF's uniform softmax: each context row = the mean of V over its l keys.
 mmr_status mmr_bert_attention(const uint16_t* qkv, const int64_t* mask01, uint16_t* ctx, int32_t b, int32_t l,
                               int32_t h, int32_t dh, void* stream) {
   mmr::clear_error();
