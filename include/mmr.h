@@ -106,9 +106,11 @@ mmr_status mmr_index_link_graph(mmr_index* index, double threshold, int32_t max_
  * gamma*minmax(cos(kg vectors)) — cosines in f64, 0 for a zero norm — and the first topk written
  * in final-score order (equal finals: later candidate first, as np.argsort(final)[::-1]).
  * q_emb (nq, d) f32; q_labels (nq) / g_labels (n) uint64 label bitsets; q_kg (nq, dk) /
- * g_kg (n, dk) f32 record KG vectors (g_* in local row order).  Outputs (nq, topk): out_idx int64
- * (-1 beyond the valid candidates), optional out_final / out_emb / out_lab / out_kg f64 (the
- * scaled components, like the reference's result tuples). */
+ * g_kg (n, dk) f32 record KG vectors (g_* in local row order).  Outputs (nq, topk): out_idx int64,
+ * optional out_final / out_emb / out_lab / out_kg f64 (the scaled components, like the reference's
+ * result tuples).  A candidate is valid when it is >= 0 and a row of this index ([idx_base,
+ * idx_base + n)); the min-max runs over the valid candidates only, and every output slot past their
+ * number is written: out_idx -1, the f64 outputs 0.0. */
 mmr_status mmr_index_rerank(const mmr_index* index, const float* q_emb, int64_t nq, const int64_t* cand,
                             int32_t kc, const uint64_t* q_labels, const uint64_t* g_labels, const float* q_kg,
                             const float* g_kg, int32_t dk, double alpha, double beta, double gamma,
@@ -116,8 +118,11 @@ mmr_status mmr_index_rerank(const mmr_index* index, const float* q_emb, int64_t 
                             double* out_lab, double* out_kg, void* stream);
 
 /* Merge n_lists per-shard lists laid out [n_lists][nq][k_in] (f64 scores, int64 idx; empty slots
- * idx -1) into the global top-k_out per query: score desc, then index asc.  out_score f32 (may be
- * NULL), out_score64 f64 (may be NULL). */
+ * idx -1, anywhere in a list, their scores ignored) into the global top-k_out per query: score desc,
+ * then index asc, then source position (list, slot) asc — an entry that two lists deliver with the
+ * same score and index is kept twice, in source order, each with its own payload.  Slots past the
+ * valid entries are (-1, -inf, zero payload).  n_lists * k_in <= 4096.  out_score f32 (may be NULL),
+ * out_score64 f64 (may be NULL). */
 mmr_status mmr_merge_topk(const double* scores, const int64_t* idx, int32_t n_lists, int64_t nq,
                           int32_t k_in, int32_t k_out, int64_t* out_idx, float* out_score,
                           double* out_score64, void* stream);

@@ -1917,7 +1917,9 @@ __global__ __launch_bounds__(T) void knn_select_t(
 // sharded rerank's per-candidate components, computed on the shard that owns the row).  Entry e's
 // score / index / payload sit at scores[e * ss], idx[e * si], pay[e * sp + p]: separate arrays
 // (1, 1, P) or ONE packed all-gather buffer of 8-byte words [n_lists][nq_total][k_in][W] = {f64 score,
-// int64 index, P f64 payload} (W, W, W: mmr_merge_topk_packed).
+// int64 index, P f64 payload} (W, W, W: mmr_merge_topk_packed).  Rank: score desc, index asc, source
+// position asc (unique per valid entry: no two entries share an output slot); slots past the valid
+// entries get (-1, -inf, zero payload).
 __global__ __launch_bounds__(256) void knn_merge(const double* __restrict__ scores,
                                                  const int64_t* __restrict__ idx, int n_lists,
                                                  int64_t nq_total, int64_t q0, int k_in, int k_out,
@@ -1949,7 +1951,8 @@ __global__ __launch_bounds__(256) void knn_merge(const double* __restrict__ scor
       const int64_t ij = ci[j];
       if (ij < 0) continue;
       const double sj = cs[j];
-      rank += (sj > sc) || (sj == sc && ij < ic);
+      // source position last: the same (score, index) delivered by two lists keeps both, in source order
+      rank += (sj > sc) || (sj == sc && (ij < ic || (ij == ic && j < c)));
     }
     if (rank < k_out) {
       out_idx[qi * k_out + rank] = ic;
@@ -2068,7 +2071,8 @@ __device__ RerankRaw rerank_raw(const float* __restrict__ qe, int d, const float
   return r;
 }
 
-// min-max over the valid lanes, mix, rank (final desc, equal finals: later candidate first), write
+// min-max over the valid lanes, mix, rank (final desc, equal finals: later candidate first), write;
+// slots past the valid candidates get -1 / 0.0 in every output given
 __device__ void rerank_mix_out(double e, double lab, double kgs, bool valid, int64_t gidx, double wa, double wb,
                                double wg, int topk, int64_t qi, int lane, int64_t* __restrict__ out_idx,
                                double* __restrict__ out_final, double* __restrict__ out_emb,
@@ -2091,7 +2095,14 @@ __device__ void rerank_mix_out(double e, double lab, double kgs, bool valid, int
   }
   int nvalid = 0;
   for (int j = 0; j < 64; ++j) nvalid += __shfl((int)valid, j, 64);
-  for (int r = nvalid + lane; r < topk; r += 64) out_idx[qi * topk + r] = -1;
+  for (int r = nvalid + lane; r < topk; r += 64) {  // past the valid candidates: -1 and zeros
+    const int64_t o = qi * topk + r;
+    out_idx[o] = -1;
+    if (out_final) out_final[o] = 0.0;
+    if (out_emb) out_emb[o] = 0.0;
+    if (out_lab) out_lab[o] = 0.0;
+    if (out_kg) out_kg[o] = 0.0;
+  }
 }
 
 __global__ __launch_bounds__(64) void knn_rerank(

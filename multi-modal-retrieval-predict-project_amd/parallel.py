@@ -38,7 +38,8 @@ def shard_bounds(n, world):
 
 def merge_topk_host(scores64, idx, k_out, payload=None):
     """Same merge as the HIP kernel (mmr_merge_topk[_payload]) for host-resident lists [L][B][k_in]
-    (a CPU coordinator, or the gloo test path): score desc, index asc, idx -1 = empty; payload
+    (a CPU coordinator, or the gloo test path): score desc, index asc, then source position (the same
+    (score, index) from two lists is kept twice, in list order), idx -1 = empty; payload
     [L][B][k_in][P] rides with each entry (4th output (B, k_out, P), zeros for empty slots)."""
     L_, B, k_in = idx.shape
     src = torch.arange(L_ * k_in).view(1, -1).expand(B, -1)

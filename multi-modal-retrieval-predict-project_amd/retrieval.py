@@ -188,7 +188,8 @@ class GalleryIndex:
     def rerank(self, q_emb, cand, q_labels, g_labels, q_kg, g_kg, topk, alpha=0.6, beta=0.25, gamma=0.15,
                want_components=True):
         """Fused KG / label rerank of device top-K candidates (mmr_index_rerank).  Returns
-        (idx (nq, topk) int64, final, emb_n, lab_n, kg_n (nq, topk) f64 or None)."""
+        (idx (nq, topk) int64, final, emb_n, lab_n, kg_n (nq, topk) f64 or None); past the valid
+        candidates of a query (cand -1 or not a row of this index) idx is -1 and the rest 0.0."""
         q_emb = q_emb.to(torch.float32).contiguous()
         nq, kc = cand.shape
         dev = cand.device
