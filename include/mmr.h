@@ -215,8 +215,16 @@ int32_t mmr_linear_bf16_n_variants(void);
  *                      or -1 = automatic (default).
  *   MMR_PIN_X3_MLP:    value = 0 (8-wave workgroups) or 1 (4-wave workgroups, two per CU) for
  *                      mmr_x3_swin_mlp at C = 96, or -1 = automatic (1).  Both give bit-identical outputs.
+ *   MMR_PIN_SWA:       route of mmr_swin_window_attention: 0 = the gather kernel, 1 = the streaming kernel
+ *                      wherever it takes the geometry (7 x 7 windows, an even number of heads; any other
+ *                      geometry, and the _q8 form, stay on the gather kernel), -1 = automatic (default: the
+ *                      streaming kernel from 3 units per wave up).  Both give bit-identical outputs.
+ *                      Launch rule of the streaming kernel: units = b * (hw / 7)^2 * (heads / 2), ordered
+ *                      (window, head pair)-major with the images innermost; workgroups of 4 waves,
+ *                      min(CUs, ceil(units / 4)) of them; wave g of the G = 4 * workgroups takes the units
+ *                      [g * units / G, (g + 1) * units / G) (integer division).
  * MMR_ERR_INVALID for an unknown pin or value. */
-enum { MMR_PIN_GEMM_BF16 = 0, MMR_PIN_X3_WAVES = 1, MMR_PIN_X3_MLP = 2 };
+enum { MMR_PIN_GEMM_BF16 = 0, MMR_PIN_X3_WAVES = 1, MMR_PIN_X3_MLP = 2, MMR_PIN_SWA = 3 };
 mmr_status mmr_pin_variant(int32_t which, int32_t value);
 
 /* Resident-weight streaming linear for the short-K, narrow tower linears (Swin patch embed, stage-2

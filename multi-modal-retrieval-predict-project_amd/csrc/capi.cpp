@@ -20,6 +20,7 @@ void clear_error() { g_err[0] = 0; }
 std::atomic<int> pin_gemm_bf16{-1};
 std::atomic<int> pin_x3_waves{-1};
 std::atomic<int> pin_x3_mlp{-1};
+std::atomic<int> pin_swa{-1};
 }  // namespace mmr
 
 extern "C" {
@@ -42,6 +43,11 @@ mmr_status mmr_pin_variant(int32_t which, int32_t value) {
   if (which == MMR_PIN_X3_MLP) {
     MMR_REQUIRE(value >= -1 && value <= 1, "mmr_pin_variant: x3 mlp form %d (-1, 0, 1)", value);
     mmr::pin_x3_mlp.store(value);
+    return MMR_OK;
+  }
+  if (which == MMR_PIN_SWA) {
+    MMR_REQUIRE(value >= -1 && value <= 1, "mmr_pin_variant: window attention route %d (-1, 0, 1)", value);
+    mmr::pin_swa.store(value);
     return MMR_OK;
   }
 

@@ -16,6 +16,20 @@ void clear_error();
 extern std::atomic<int> pin_gemm_bf16;
 extern std::atomic<int> pin_x3_waves;
 extern std::atomic<int> pin_x3_mlp;
+extern std::atomic<int> pin_swa;
+
+// Streaming route of mmr_swin_window_attention (swin_wattn.hip).  Launch rule (mmr.h): persistent
+// workgroups of SWA_STREAM_WAVES waves, min(CUs, ceil(units / waves)) of them, units = images x windows x
+// head pairs; wave g of the G = workgroups * waves takes the units [g units / G, (g + 1) units / G)
+constexpr int SWA_STREAM_WAVES = 4;
+inline int64_t swa_stream_grid(int64_t units, int cus) {
+  const int64_t need = (units + SWA_STREAM_WAVES - 1) / SWA_STREAM_WAVES;
+  return need < cus ? need : cus;
+}
+bool swa_stream_takes(int64_t b, int hw, int c, int heads, int ws);  // the geometries the kernel is built for
+bool swa_stream_auto(int64_t b, int hw, int heads);                  // ... and where the automatic route uses it
+mmr_status swa_stream_launch(const uint16_t* qkv, const float* bias, uint16_t* out, int32_t b, int32_t hw, int32_t c,
+                             int32_t heads, int32_t shift, void* stream);
 
 inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
 

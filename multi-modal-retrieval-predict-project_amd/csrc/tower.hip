@@ -1059,6 +1059,14 @@ static mmr_status swin_window_attention_launch(const uint16_t* qkv, const float*
   if (b == 0) return MMR_OK;
   MMR_REQUIRE((int64_t)b * hw * hw * 3 * c < ((int64_t)1 << 32), "mmr_swin_window_attention: %lld qkv elements (32-bit offsets)",
               (long long)b * hw * hw * 3 * c);
+  // the streaming route (swin_wattn.hip; bit-identical output) for the geometries it is built for: where
+  // it measured faster (swa_stream_auto), or pinned on / off (MMR_PIN_SWA 1 / 0).  The MX-fp8 form stays
+  // on the gather kernel
+  if (!q8 && mmr::swa_stream_takes(b, hw, c, heads, ws)) {
+    const int pin = mmr::pin_swa.load(std::memory_order_relaxed);
+    if (pin == 1 || (pin < 0 && mmr::swa_stream_auto(b, hw, heads)))
+      return mmr::swa_stream_launch(qkv, bias, out, b, hw, c, heads, shift, stream);
+  }
   // one head per wave: the head pairs (hpw = 2, a wave reading whole 128-B lines) serialise two load
   // round trips per wave, and the pair's halves of a line are read by adjacent waves of one workgroup
   // anyway (6 / 12 / 24 heads, 4 waves per workgroup): in the cfg2 step stage 2 131 -> 116 us, at
