@@ -656,6 +656,33 @@ mmr_status mmr_x3_mean_rows(const float* x, const float* extra, float* y, int32_
 /* y (b, c) = x[i*ldx + 0..c), f32 (the CLS rows, fusion.py:447). */
 mmr_status mmr_x3_gather_rows(const float* x, int64_t ldx, float* y, int32_t b, int32_t c, void* stream);
 
+/* ---------------------------------------------------------------- classifier head / predict() tail */
+/* The reference's classification head on the joint embedding and the tail of its predict()
+ * (src/Model/model.py:271-277, 481, 491-537), eval (the Dropouts are identities), csrc/cls_head.hip:
+ *   logits (b, c) f32 = W2 GELU_erf(W1 x + b1) + b2,  W1 [h][d], W2 [c][h]
+ *   probs  (b, c) f32 = 1 / (1 + exp(-logits))
+ *   preds  (b, c) i32 = probs >= threshold
+ *   topk_vals / topk_idx (b, k) f32 / i32: the k largest probs per row, ordered by (prob desc, class asc)
+ * One precision whatever the tower mode: f32 activations, both contractions on bf16x3 MFMA (as
+ * mmr_linear_x3), no atomics, and a row's logits do not depend on the rest of the batch (same bits for any
+ * b).  d % 128 == 0, d <= 1024, h == 4 d runs one fused pass with the hidden kept on chip plus a finishing
+ * pass; other geometries (d % 16 == 0, h % 32 == 0) run mmr_linear_x3 / mmr_linear_f32 twice and the same
+ * finishing pass.  1 <= c <= 256 (beyond: MMR_ERR_UNSUPPORTED); x rows f32 at stride ldx (>= d, % 4 == 0),
+ * 16-B aligned.
+ * images: mmr_classifier_pack_bytes(d, h, c) bytes (0: geometry not built), built once from the f32
+ *   weights by mmr_classifier_pack; the layout is private to the library.
+ * work:   mmr_classifier_work_bytes(b, d, h, c) bytes of scratch, owned by the caller, 16-B aligned.
+ * probs, preds, topk_vals, topk_idx may each be NULL (not computed / not written); with a top-K output
+ * 1 <= k <= c.  All outputs are dense.  b == 0: no launch. */
+int64_t mmr_classifier_pack_bytes(int32_t d, int32_t h, int32_t c);
+mmr_status mmr_classifier_pack(const float* w1, const float* w2, void* images, int32_t d, int32_t h, int32_t c,
+                               void* stream);
+int64_t mmr_classifier_work_bytes(int32_t b, int32_t d, int32_t h, int32_t c);
+mmr_status mmr_classifier_head(const float* x, int64_t ldx, const void* images, const float* b1, const float* b2,
+                               void* work, float* logits, float* probs, int32_t* preds, float* topk_vals,
+                               int32_t* topk_idx, int32_t b, int32_t d, int32_t h, int32_t c, int32_t k,
+                               float threshold, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -6,6 +6,7 @@ Backbones.forward(image, input_ids, attention_mask) -> ((img_global, img_patches
     norm, so patches are LayerNorm'd twice — and img_global = mean of the once-normed tokens;
     txt_feats = BertModel(...).last_hidden_state (truncated to max_position_embeddings).
 MultiModalRetrievalModel.forward(...) -> {"joint_emb", "img_emb", "txt_emb", "logits", "attn"}
+MultiModalRetrievalModel.predict(...) -> {"probs", "preds", "topk_idx", "topk_vals"}
     model.py:365-373: img_emb = img_proj(img_global); txt_emb = txt_proj(mean over ALL L tokens,
     PAD included) (CLS only with use_cls_only).
     model.py:462-479 heads: "text"  joint = ffn0(txt_proj(mean(txt)))
@@ -14,10 +15,16 @@ MultiModalRetrievalModel.forward(...) -> {"joint_emb", "img_emb", "txt_emb", "lo
     ffn0 = MultiHeadMLP (Linear D->2D, GELU, Linear 2D->D), model.py:61-75; shared_ffn when
     use_shared_ffn (reference default True, configs/config.yaml false).
     "multimodal" = num_fusion_layers x CrossModalFusion (fusion.py:334-471) + combiner
-    (model.py:375-459) on libmmr kernels (mmr_amd/fusion.py); the classifier (logits) is
-    classification, out of scope -> None; return_attention=True fills "attn" with the reference's
-    head-averaged maps layer_{i}_comb / _txt2img / _img2txt (model.py:399-420, CPU f32 tensors; {} for
-    the image / text heads, None without the flag).
+    (model.py:375-459) on libmmr kernels (mmr_amd/fusion.py); return_attention=True fills "attn" with
+    the reference's head-averaged maps layer_{i}_comb / _txt2img / _img2txt (model.py:399-420, CPU f32
+    tensors; {} for the image / text heads, None without the flag).
+    logits = classifier(joint_emb) (model.py:271-277, 481: Linear D->4D, GELU, Linear 4D->C; the Dropouts
+    are eval identities) as a (B, C) f32 device tensor when the head state / checkpoint carries
+    classifier.0.* / classifier.3.* (ops.classifier_head, one fused pass), else None.
+    predict() (model.py:491-537): sigmoid probabilities, thresholded multi-label predictions and the
+    top-K labels per query, all from the same kernel pass; explain=True (Integrated Gradients / Grad-CAM,
+    which need autograd and Captum) is left out — return_attention=True and retrieve=True give the
+    attention maps and the retrieved neighbours.
 """
 import collections
 import json
@@ -222,7 +229,7 @@ class MultiModalRetrievalModel:
     """src/Model/model.py:114-328 MultiModalRetrievalModel (inference) on libmmr kernels.
 
     Reference arguments (model.py:116-137), same names, order and defaults: joint_dim, num_heads,
-    num_classes (the classifier is classification, out of scope: accepted, logits None),
+    num_classes (the classifier weights decide it when present; without them logits is None),
     num_fusion_layers, fusion_type ("cross" only, as in the reference), img_backbone, swin_name,
     cnn_name, bert_name, img_dim, txt_dim, swin_ckpt_path, bert_local_dir, pretrained,
     checkpoint_path (a state dict of the whole reference model, loaded with torch.load(...,
@@ -300,6 +307,14 @@ class MultiModalRetrievalModel:
             self.fusion = FusionStack(hs, num_heads, device=self.device, use_shared_ffn=use_shared_ffn,
                                       tower_dtype=getattr(self.backbones, "tower_dtype", tower_dtype))
         self.num_fusion_layers = num_fusion_layers
+        # model.py:271-277 classifier: Linear(D, 4D), GELU, Dropout, Linear(4D, C), Dropout (eval: identities)
+        self.classifier = None
+        if "classifier.0.weight" in hs:
+            self.classifier = ops.ClassifierW(f("classifier.0.weight"), f("classifier.0.bias"),
+                                              f("classifier.3.weight"), f("classifier.3.bias"))
+            if self.classifier.d != joint_dim:
+                raise ValueError(f"classifier.0.weight takes {self.classifier.d} inputs, joint_dim is {joint_dim}")
+            self.num_classes = self.classifier.c  # the weights decide, as for num_fusion_layers
         if self.retriever is None and not training and os.environ.get("MMR_EMBEDDINGS_DIR"):
             from .retrieval import make_retrieval_engine
             d = Path(os.environ["MMR_EMBEDDINGS_DIR"])
@@ -331,6 +346,12 @@ class MultiModalRetrievalModel:
         return ops.proj_head(x, proj[0], proj[1], *self.ffn, l2norm=l2norm)
 
     def forward(self, image, input_ids, attention_mask, return_attention=False):
+        out = self._forward(image, input_ids, attention_mask, return_attention)
+        if self.classifier is not None:  # model.py:481
+            out["logits"] = ops.classifier_head(out["joint_emb"], self.classifier)["logits"]
+        return out
+
+    def _forward(self, image, input_ids, attention_mask, return_attention=False):
         mm = self.model_type == "multimodal"
         img_global = patches = pool = txt_mean = txt = None
         if image is not None:
@@ -355,6 +376,38 @@ class MultiModalRetrievalModel:
         return {"joint_emb": joint, "img_emb": img_emb, "txt_emb": txt_emb, "logits": None, "attn": attn}
 
     __call__ = forward
+
+    def predict(self, image, input_ids, attention_mask, threshold=0.5, K=5, explain=False, *, retrieve=False):
+        """model.py:491-537 predict (names, order and defaults are the reference's): one forward plus one
+        ops.classifier_head call -> {"probs": np.float32 (B, C) sigmoid(logits), "preds": np.int32 (B, C) =
+        probs >= threshold, "topk_idx": K class indices per query (list of lists of int, by descending
+        probability, equal probabilities by ascending class), "topk_vals": their probabilities (list of lists
+        of float)}.  retrieve=True adds "retrieval_ids" / "retrieval_dists": per query what
+        self.retriever.retrieve(joint_emb[i], K=K) returns (the loop of explain(), model.py:615-623).
+        explain=True — the reference's Integrated-Gradients / Grad-CAM maps — is not part of this
+        inference-only package."""
+        if explain:
+            raise NotImplementedError(
+                "predict(explain=True): the reference's IG / Grad-CAM explanations need autograd and Captum and are "
+                "out of scope here; use forward(..., return_attention=True) for the attention maps and "
+                "predict(..., retrieve=True) for the retrieved neighbours")
+        if self.classifier is None:
+            raise ValueError("predict needs classifier.0.* / classifier.3.* weights in the checkpoint / head_state")
+        if retrieve and self.retriever is None:
+            raise ValueError("predict(retrieve=True) needs a retriever (set_retriever / retriever=)")
+        joint = self._forward(image, input_ids, attention_mask)["joint_emb"]
+        res = ops.classifier_head(joint, self.classifier, k=K, threshold=threshold,
+                                  want=("probs", "preds", "topk_vals", "topk_idx"))
+        output = {"probs": res["probs"].cpu().numpy(), "preds": res["preds"].cpu().numpy(),
+                  "topk_idx": res["topk_idx"].cpu().tolist(), "topk_vals": res["topk_vals"].cpu().tolist()}
+        if retrieve:
+            ids, dists = [], []
+            for q in joint.detach().cpu().numpy():
+                i, d = self.retriever.retrieve(q, K=K)
+                ids.append(i)
+                dists.append(d)
+            output["retrieval_ids"], output["retrieval_dists"] = ids, dists
+        return output
 
     def query_embeddings(self, image, input_ids, attention_mask):
         """Retrieval keys of one batch.  multimodal: (B, D) f32 joint embeddings of (image, report)
@@ -422,6 +475,18 @@ def init_head_state(img_dim, txt_dim, joint_dim, seed=2711):
         sd.update({pre + "linear1.weight": rn(2 * D, D), pre + "linear1.bias": rn(2 * D),
                    pre + "linear2.weight": rn(D, 2 * D), pre + "linear2.bias": rn(D)})
     return sd
+
+
+def init_classifier_state(joint_dim, num_classes=22, seed=2713):
+    """Random classifier weights under the reference's keys (model.py:271-277: classifier.0 Linear(D, 4D),
+    classifier.3 Linear(4D, C)) with nn.Linear-like fan-in scaling; its own RNG stream (init_head_state's is
+    unchanged: a model gets a classifier only when these keys are added to its head state)."""
+    g = torch.Generator().manual_seed(seed)
+    D, H = joint_dim, 4 * joint_dim
+    return {"classifier.0.weight": torch.randn(H, D, generator=g) * D ** -0.5,
+            "classifier.0.bias": torch.randn(H, generator=g) * 0.02,
+            "classifier.3.weight": torch.randn(num_classes, H, generator=g) * H ** -0.5,
+            "classifier.3.bias": torch.randn(num_classes, generator=g) * 0.02}
 
 
 def init_fusion_state(img_dim, txt_dim, joint_dim, num_heads=8, num_fusion_layers=5, seed=2712,

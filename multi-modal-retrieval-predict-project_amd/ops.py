@@ -482,6 +482,73 @@ def linear_x3_batched(x, wx, bias, nbatch, b, residual=None, act=0, out=None, ld
     return y
 
 
+class ClassifierW:
+    """The classification head's weights for classifier_head (model.py:271-277: Linear(D, H = 4D), GELU,
+    Linear(H, C); the Dropouts are eval identities): the packed weight images mmr_classifier_pack builds
+    once (private layout, as X3W holds the split) plus the two f32 biases.  w1 (H, D), b1 (H,), w2 (C, H),
+    b2 (C,) — device tensors; the f32 weights are not kept."""
+    __slots__ = ("images", "b1", "b2", "d", "h", "c")
+
+    def __init__(self, w1, b1, w2, b2):
+        _lib.require_gpu(w1)
+        w1 = w1.detach().to(torch.float32).contiguous()
+        w2 = w2.detach().to(device=w1.device, dtype=torch.float32).contiguous()
+        self.h, self.d = (int(s) for s in w1.shape)
+        self.c = int(w2.shape[0])
+        if w2.shape[1] != self.h or b1.shape != (self.h,) or b2.shape != (self.c,):
+            raise ValueError(f"classifier shapes: w1 {tuple(w1.shape)} b1 {tuple(b1.shape)} w2 {tuple(w2.shape)} "
+                             f"b2 {tuple(b2.shape)}")
+        self.b1 = b1.detach().to(device=w1.device, dtype=torch.float32).contiguous()
+        self.b2 = b2.detach().to(device=w1.device, dtype=torch.float32).contiguous()
+        nbytes = _L().mmr_classifier_pack_bytes(self.d, self.h, self.c)
+        self.images = torch.empty(max(int(nbytes), 16), dtype=torch.uint8, device=w1.device)
+        _chk(_L().mmr_classifier_pack(_lib.ptr(w1), _lib.ptr(w2), _lib.ptr(self.images), self.d, self.h, self.c,
+                                      _s(w1)), "mmr_classifier_pack")
+
+
+CLASSIFIER_OUTPUTS = ("logits", "probs", "preds", "topk_vals", "topk_idx")
+
+
+def classifier_head(x, cw, k=None, threshold=0.5, want=("logits",), out=None):
+    """The classification head and predict() tail on x (B, D) f32 rows (unit column stride) in one
+    mmr_classifier_head call: a dict with the entries of `want` out of logits (B, C) f32, probs (B, C) f32 =
+    sigmoid(logits), preds (B, C) int32 = probs >= float32(threshold), topk_vals (B, k) f32 / topk_idx
+    (B, k) int32 = the k largest probs per row in (prob desc, class asc) order (k: 1..C, needed with a
+    top-K output).  logits are always computed.  `out`: preallocated dense tensors by name."""
+    _lib.require_gpu(x)
+    assert x.dim() == 2 and x.stride(1) == 1 and x.dtype == torch.float32
+    bad = [w for w in want if w not in CLASSIFIER_OUTPUTS]
+    if bad:
+        raise ValueError(f"classifier_head: unknown outputs {bad} (known: {CLASSIFIER_OUTPUTS})")
+    B, D = x.shape
+    if D != cw.d:
+        raise ValueError(f"classifier_head: x has {D} columns, the head takes {cw.d}")
+    topk = "topk_vals" in want or "topk_idx" in want
+    if topk and (k is None or not 1 <= int(k) <= cw.c):
+        raise ValueError(f"classifier_head: k={k} outside 1..{cw.c}")
+    k = int(k) if topk else 0
+    shapes = {"logits": ((B, cw.c), torch.float32), "probs": ((B, cw.c), torch.float32),
+              "preds": ((B, cw.c), torch.int32), "topk_vals": ((B, k), torch.float32),
+              "topk_idx": ((B, k), torch.int32)}
+    res = {}
+    for name in dict.fromkeys(("logits",) + tuple(want)):
+        shape, dt = shapes[name]
+        t = (out or {}).get(name)
+        if t is None:
+            t = torch.empty(shape, dtype=dt, device=x.device)
+        elif tuple(t.shape) != shape or t.dtype != dt or not t.is_contiguous():
+            raise ValueError(f"classifier_head: out[{name!r}] must be a dense {shape} {dt} tensor")
+        res[name] = t
+    nwork = _L().mmr_classifier_work_bytes(B, cw.d, cw.h, cw.c)
+    work = torch.empty(max(int(nwork), 16), dtype=torch.uint8, device=x.device)
+    _chk(_L().mmr_classifier_head(_lib.ptr(x), x.stride(0), _lib.ptr(cw.images), _lib.ptr(cw.b1), _lib.ptr(cw.b2),
+                                  _lib.ptr(work), _lib.ptr(res["logits"]), _lib.ptr(res.get("probs")),
+                                  _lib.ptr(res.get("preds")), _lib.ptr(res.get("topk_vals")),
+                                  _lib.ptr(res.get("topk_idx")), B, cw.d, cw.h, cw.c, k, float(threshold), _s(x)),
+         "mmr_classifier_head")
+    return {name: res[name] for name in want}
+
+
 def mha(q, k, v, b, lq, lk, heads, dh, scale, out=None, mean_out=None, q8=False):
     """Attention core over strided row views: q (b*lq, >=heads*dh) etc. (unit column stride).  q8: the
     output also as an MX-fp8 activation operand, returned as (out, mean_out, MXFP8)."""
