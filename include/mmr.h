@@ -162,6 +162,39 @@ mmr_status mmr_rerank_mix(const int64_t* cand, const double* comp, int64_t nq, i
                           double beta, double gamma, int32_t topk, int64_t* out_idx, double* out_final,
                           double* out_emb, double* out_lab, double* out_kg, void* stream);
 
+/* Full-ranking label evaluation (compute_ranking_metrics, src/Evaluate/retrieval_overlap.py:84-115; the
+ * test -> test ground truth of contructGT.py:73 drops the query itself): the rank of the first gallery row that
+ * shares a label with the query, over the WHOLE gallery, and the number of such rows.  For query q and row g:
+ *   score(q, g) = <q, g> / (|q| |g|) in f64 of the raw rows (fp16 rows upcast exactly), 0 when either norm is 0
+ *     — mmr_index_search's expression.  The contraction runs on the f64 matrix unit in a summation order of its
+ *     own, so a score may differ from mmr_index_search's out_score64 in the last bits; what holds instead: the
+ *     order is the same for every (query, row) pair, for both index dtypes and in both entry points, so
+ *     byte-identical rows score bit-identically and mmr_index_count_ahead reproduces the score
+ *     mmr_index_best_relevant returned for a row bit for bit.
+ *   order: score descending, then GLOBAL index (idx_base + row) ascending — the search's order.
+ *   g is relevant iff (g_labels[g] & q_labels[q]) != 0.
+ *   g is excluded iff exclude != NULL && exclude[q] == the global index of g (exclude[q] < 0: nothing): an
+ *     excluded row is neither relevant nor counted ahead of anything.
+ *   Only rows < n exist: the padding of the device layout is masked by row number, never by score.
+ * mmr_index_best_relevant: per query the first relevant row under the order — out_idx (nq) global index, -1 when
+ *   there is none; out_score (nq, may be NULL) its score, 0.0 when none — and out_nrel (nq, may be NULL) the number
+ *   of relevant rows.  q (nq, d) f32; q_labels (nq) / g_labels (n, this index's rows in local order) uint64 bitsets.
+ * mmr_index_count_ahead: per query the number of this index's existing, non-excluded rows ranked strictly ahead of
+ *   (ref_score, ref_idx): score > ref_score, or score == ref_score and global index < ref_idx.  ref_idx is a global
+ *   index and need not be a row of this index (row-sharded galleries: every shard counts against the global best
+ *   and the counts add up); ref_idx[q] < 0: out_ahead[q] = 0 and no work for that query.
+ *   first_rank = 1 + count_ahead(best_relevant), 0 when there is no relevant row.
+ * work: mmr_index_rank_work_bytes(index, nq) bytes of scratch owned by the caller, 16-B aligned (the index is
+ *   const: neither call touches its search workspace).  Any nq (queries run in internal passes); nq == 0 launches
+ *   nothing.  All pointers device, asynchronous on `stream`.  No atomics: two runs give identical bytes. */
+int64_t mmr_index_rank_work_bytes(const mmr_index* index, int64_t nq);
+mmr_status mmr_index_best_relevant(const mmr_index* index, const float* q, int64_t nq, const uint64_t* q_labels,
+                                   const uint64_t* g_labels, const int64_t* exclude, int64_t* out_idx,
+                                   double* out_score, int64_t* out_nrel, void* work, void* stream);
+mmr_status mmr_index_count_ahead(const mmr_index* index, const float* q, int64_t nq, const int64_t* ref_idx,
+                                 const double* ref_score, const int64_t* exclude, int64_t* out_ahead, void* work,
+                                 void* stream);
+
 /* ---------------------------------------------------------------- tower ops (bf16 = uint16) */
 /* Y[m][n] = act(X[m][k] . W[n][k]^T + bias[n]) (+ R[m][n]); X, W, R, Y bf16; bias f32 or NULL;
  * act: 0 none, 1 GELU(erf).  nn.Linear semantics (weight [out][in]).  f32 accumulation. */

@@ -35,6 +35,9 @@ SIGNATURES = {
                                c_vp, c_vp],
     "mmr_merge_topk_packed": [c_vp, c_i32, c_i32, c_i64, c_i64, c_i64, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp],
     "mmr_index_rerank_components": [c_vp, c_vp, c_i64, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp],
+    "mmr_index_rank_work_bytes": [c_vp, c_i64],
+    "mmr_index_best_relevant": [c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp],
+    "mmr_index_count_ahead": [c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp],
     "mmr_rerank_mix": [c_vp, c_vp, c_i64, c_i32, ctypes.c_double, ctypes.c_double, ctypes.c_double, c_i32, c_vp, c_vp,
                        c_vp, c_vp, c_vp, c_vp],
     "mmr_linear_bf16": [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i32, c_i32, c_i32, c_vp],
@@ -143,7 +146,10 @@ _RESTYPES = {"mmr_last_error": ctypes.c_char_p, "mmr_version": ctypes.c_int, "mm
              "mmr_x3_swin_mlp_pack_elems": ctypes.c_int64, "mmr_x3_rowlin_pack_elems": ctypes.c_int64,
              "mmr_x3_patch_embed_pack_elems": ctypes.c_int64,
              "mmr_x3_swin_attn_block_pack_bytes": ctypes.c_int64,
-             "mmr_classifier_pack_bytes": ctypes.c_int64, "mmr_classifier_work_bytes": ctypes.c_int64}
+             "mmr_classifier_pack_bytes": ctypes.c_int64, "mmr_classifier_work_bytes": ctypes.c_int64,
+             "mmr_index_rank_work_bytes": ctypes.c_int64}
+
+ABI_VERSION = 2  # mmr_version() this binding is written against (2: the full-ranking evaluation entry points)
 
 _lib = None
 
@@ -159,6 +165,10 @@ def lib():
         if not os.path.exists(LIB_PATH):
             raise MMRError(f"{LIB_PATH} is not built: run `python -c 'import __graft_entry__ as g; g.build()'`")
         L = ctypes.CDLL(LIB_PATH)
+        L.mmr_version.restype = ctypes.c_int
+        if L.mmr_version() < ABI_VERSION:  # a stale build would take calls with another argument list
+            raise MMRError(f"{LIB_PATH} reports C-ABI version {L.mmr_version()}, this package needs >= {ABI_VERSION}: "
+                           f"rebuild it (`python -c 'import __graft_entry__ as g; g.build()'`)")
         for name, args in SIGNATURES.items():
             if not hasattr(L, name):  # a call to a missing export raises AttributeError
                 continue

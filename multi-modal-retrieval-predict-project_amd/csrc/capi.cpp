@@ -25,7 +25,7 @@ std::atomic<int> pin_swa{-1};
 
 extern "C" {
 const char* mmr_last_error(void) { return mmr::g_err; }
-int mmr_version(void) { return 1; }
+int mmr_version(void) { return 2; }
 
 mmr_status mmr_pin_variant(int32_t which, int32_t value) {
   mmr::clear_error();

@@ -17,12 +17,22 @@ it must run after the merge): each shard computes its candidates' raw {emb cosin
 cosine} where the rows and tables live (mmr_index_rerank_components), the components ride with the
 (score, index) lists through the same all-gather and the merge (mmr_merge_topk_payload), and the
 min-max / mix / rank runs on the merged list (mmr_rerank_mix) — bit-identical to one index.
+Sharded full-ranking evaluation (ShardedIndex.rank_eval; compute_ranking_metrics,
+src/Evaluate/retrieval_overlap.py:84-115, over a row-sharded gallery), two phases after the query all-gather:
+  1. every shard finds its first relevant row and its relevant count (mmr_index_best_relevant); ONE all-gather
+     of {f64 score, int64 index bits, int64 count bits} per query; every rank takes the global best under
+     (score desc, global index asc) and the summed count,
+  2. every shard counts its rows ranked ahead of that global best (mmr_index_count_ahead: the reference row may
+     live on another shard); ONE all-gather of the counts, summed: first_rank = 1 + the sum.
+Equal to the one-index result: the shards' scores are the one index's (same contraction order) and the order is
+on global indices.
 """
 import numpy as np
 import torch
 import torch.distributed as dist
 
-from .retrieval import GalleryIndex, RetrievalEngine, merge_topk_packed, rerank_mix
+from .retrieval import (GalleryIndex, RetrievalEngine, bits_tensor, drop_excluded, list_flags, merge_topk_packed,
+                        rerank_mix)
 
 
 def shard_bounds(n, world):
@@ -144,7 +154,8 @@ class ShardedIndex:
     mode switch inside a collective: ADVICE r03; no rank raising alone before it: ADVICE r04)."""
 
     def __init__(self, gallery_rows, n_total, start, group=None, device=None, local_search=None, mode="x3",
-                 fallback_search=None, local_components=None, index=None, status_out=None):
+                 fallback_search=None, local_components=None, index=None, status_out=None,
+                 local_best_relevant=None, local_count_ahead=None):
         """index: an existing GalleryIndex of this rank's rows (instead of building one from
         gallery_rows).  status_out: a device int32 scalar that accumulates the max per-query
         search status without a host sync (a benchmark loop checks it once afterwards; the
@@ -172,6 +183,10 @@ class ShardedIndex:
         self.fallback_search = fallback_search
         self.local_components = local_components  # (q, cand) -> (nq, kc, 3) raw rerank components
         self.reruns = 0  # queries re-run through fallback_search (diagnostic)
+        # rank_eval's two local steps (tests inject host forms): (q, q_bits, g_bits, exclude) -> (idx, f64
+        # score, n_rel) of this shard; (q, ref_idx, ref_score, exclude) -> rows of this shard ranked ahead
+        self.local_best_relevant = local_best_relevant
+        self.local_count_ahead = local_count_ahead
 
     def _index_search(self, q, k):
         i, _, s64, st = self.index.search(q, k, want_f64=True, want_status=True)
@@ -271,6 +286,37 @@ class ShardedIndex:
             return rerank_mix(mi, mc, topk, alpha, beta, gamma)
         return rerank_mix_host(mi, mc, topk, alpha, beta, gamma)
 
+    def rank_eval(self, q_local, q_bits=None, g_bits=None, exclude=None):
+        """Collective full-ranking evaluation: every rank passes its own (b, D) queries; q_bits / exclude cover
+        ALL world * b queries in all-gather order (exclude: global indices, -1 = none, or None), g_bits this
+        shard's rows.  -> this rank's (first_rank (b,) int64, 0 = no relevant row; n_rel; best_idx global, -1 =
+        none; best_score f64) over the whole gallery — equal to GalleryIndex.rank_eval of one index holding it.
+        Three collectives: the queries, the shards' bests, the shards' counts."""
+        b = q_local.shape[0]
+        allq = self._gather_queries(q_local)
+        if self.local_best_relevant is not None:
+            bi, bs, nr = self.local_best_relevant(allq, q_bits, g_bits, exclude)
+        else:
+            bi, bs, nr = self.index.best_relevant(allq, q_bits, g_bits, exclude)
+        as_f64 = lambda t: t.to(torch.int64).contiguous().view(torch.float64)  # noqa: E731  (bits, as pack_lists)
+        g = self._gather(torch.stack([bs.to(torch.float64), as_f64(bi), as_f64(nr)], -1).contiguous())
+        gi = g[..., 1].contiguous().view(torch.int64)                          # (world, Q)
+        none = torch.iinfo(torch.int64).max
+        gs = torch.where(gi >= 0, g[..., 0], torch.full_like(g[..., 0], -float("inf")))
+        smax = gs.max(0).values
+        ikey = torch.where((gi >= 0) & (gs == smax[None]), gi, torch.full_like(gi, none)).min(0).values
+        best_i = torch.where(ikey == none, torch.full_like(ikey, -1), ikey)
+        best_s = torch.where(best_i >= 0, smax, torch.zeros_like(smax))
+        n_rel = g[..., 2].contiguous().view(torch.int64).sum(0)
+        if self.local_count_ahead is not None:
+            ahead = self.local_count_ahead(allq, best_i, best_s, exclude)
+        else:
+            ahead = self.index.count_ahead(allq, best_i, best_s, exclude)
+        total = self._gather(ahead.to(torch.int64).contiguous().view(-1, 1)).sum(0).view(-1)
+        first = torch.where(best_i >= 0, total + 1, torch.zeros_like(total))
+        mine = slice(self.rank * b, (self.rank + 1) * b)
+        return first[mine], n_rel[mine], best_i[mine], best_s[mine]
+
 
 class ShardedRetrievalEngine(RetrievalEngine):
     """make_retrieval_engine(method="mi355x_sharded"): every rank mmaps the .npy, keeps its row
@@ -300,3 +346,24 @@ class ShardedRetrievalEngine(RetrievalEngine):
     def retrieve(self, query_emb, K=5, **kwargs):
         idx, sc = self.search(np.asarray(query_emb, np.float32).reshape(1, -1), K)
         return [self.ids[j] for j in idx[0].tolist()], [float(x) for x in sc[0].tolist()]
+
+    def evaluate(self, Q, query_bits, gallery_bits, ks=(1, 5, 10), exclude_ids=None):
+        """MI355XRetrievalEngine.evaluate over the row-sharded gallery (collective: every rank passes its own
+        queries, the same number on every rank; gallery_bits (N,) covers the whole gallery, exclude_ids are
+        gallery rows, -1 = none).  -> this rank's queries' metrics.evaluation_summary dict."""
+        from .metrics import evaluation_summary
+        sh = self.sharded
+        q = torch.as_tensor(np.asarray(Q, np.float32) if not isinstance(Q, torch.Tensor) else Q).to("cuda", torch.float32)
+        dev, b = q.device, q.shape[0]
+        qb, gb = bits_tensor(query_bits, dev), bits_tensor(gallery_bits, dev)
+        ex = torch.full((b,), -1, dtype=torch.int64, device=dev) if exclude_ids is None else \
+            torch.as_tensor(np.asarray(exclude_ids, np.int64)).to(dev)
+        tables = sh._gather(torch.stack([qb, ex], -1).contiguous()).view(-1, 2)   # every rank's (bits, exclude)
+        k_eff = min(max(ks) + (0 if exclude_ids is None else 1), len(self.ids))
+        idx, _, _ = sh.search(q, k_eff)
+        if exclude_ids is not None:
+            idx = drop_excluded(idx, ex)
+        n0 = sh.start
+        first_rank, n_rel, _, _ = sh.rank_eval(q, tables[:, 0].contiguous(), gb[n0:n0 + sh.index.n].contiguous(),
+                                               tables[:, 1].contiguous())
+        return evaluation_summary(list_flags(idx, qb, gb), first_rank, n_rel, ks)

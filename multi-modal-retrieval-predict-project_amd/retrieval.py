@@ -214,6 +214,56 @@ class GalleryIndex:
             "mmr_index_rerank_components")
         return comp
 
+    # ---- full-ranking label evaluation (mmr_index_best_relevant / mmr_index_count_ahead) ----
+    def _rank_args(self, q, exclude):
+        _lib.require_gpu(q)
+        if q.dim() != 2 or q.shape[1] != self.d:
+            raise ValueError(f"query shape {tuple(q.shape)} does not match gallery dim {self.d}")
+        q = q.to(torch.float32).contiguous()
+        nbytes = int(_lib.lib().mmr_index_rank_work_bytes(self._h, q.shape[0]))
+        work = torch.empty((max(nbytes, 16),), dtype=torch.uint8, device=q.device)  # caller-owned scratch
+        ex = None if exclude is None else exclude.to(q.device, torch.int64).contiguous()
+        return q, work, ex
+
+    def best_relevant(self, q, q_bits, g_bits, exclude=None):
+        """Per query the first row of THIS index, in the search's order (exact cosine desc, global index
+        asc), that shares a label bit with it, and the number of such rows.  q (B, D) f32; q_bits (B,) /
+        g_bits (n,) label bitsets (uint64 carried as int64) on the device; exclude (B,) int64 global
+        indices (-1 = none) of rows that do not exist for that query (the test -> test protocol drops the
+        query itself).  -> (idx (B,) int64 global, -1 = none; score (B,) f64, 0.0 when none; n_rel (B,) int64)."""
+        q, work, ex = self._rank_args(q, exclude)
+        B, dev = q.shape[0], q.device
+        if q_bits.shape[0] != B or g_bits.shape[0] != self.n:
+            raise ValueError(f"label bitsets ({q_bits.shape[0]}, {g_bits.shape[0]}) do not match ({B}, {self.n})")
+        idx = torch.empty((B,), dtype=torch.int64, device=dev)
+        sc = torch.empty((B,), dtype=torch.float64, device=dev)
+        nrel = torch.empty((B,), dtype=torch.int64, device=dev)
+        _lib.check(_lib.lib().mmr_index_best_relevant(
+            self._h, _lib.ptr(q), B, _lib.ptr(q_bits.contiguous()), _lib.ptr(g_bits.contiguous()), _lib.ptr(ex),
+            _lib.ptr(idx), _lib.ptr(sc), _lib.ptr(nrel), _lib.ptr(work), _lib.stream_ptr(dev)),
+            "mmr_index_best_relevant")
+        return idx, sc, nrel
+
+    def count_ahead(self, q, ref_idx, ref_score, exclude=None):
+        """Per query the number of this index's rows (excluded row left out) ranked strictly ahead of
+        (ref_score, ref_idx): score > ref_score, or == and global index < ref_idx.  ref_idx (B,) int64
+        global (it may be a row of another shard; < 0: count 0), ref_score (B,) f64 -> (B,) int64."""
+        q, work, ex = self._rank_args(q, exclude)
+        B, dev = q.shape[0], q.device
+        out = torch.empty((B,), dtype=torch.int64, device=dev)
+        _lib.check(_lib.lib().mmr_index_count_ahead(
+            self._h, _lib.ptr(q), B, _lib.ptr(ref_idx.to(dev, torch.int64).contiguous()),
+            _lib.ptr(ref_score.to(dev, torch.float64).contiguous()), _lib.ptr(ex), _lib.ptr(out), _lib.ptr(work),
+            _lib.stream_ptr(dev)), "mmr_index_count_ahead")
+        return out
+
+    def rank_eval(self, q, q_bits, g_bits, exclude=None):
+        """compute_ranking_metrics' per-query quantities over the whole index (retrieval_overlap.py:84-115):
+        -> (first_rank (B,) int64: 1-based rank of the first relevant row, 0 = none; n_rel; best_idx; best_score)."""
+        idx, sc, nrel = self.best_relevant(q, q_bits, g_bits, exclude)
+        ahead = self.count_ahead(q, idx, sc, exclude)
+        return torch.where(idx >= 0, ahead + 1, torch.zeros_like(ahead)), nrel, idx, sc
+
     def close(self):
         h, self._h = getattr(self, "_h", None), None
         if h:
@@ -274,6 +324,28 @@ def merge_topk_packed(packed: torch.Tensor, k_out: int, payload_width: int = 0, 
     return (oi, os_, o64) if op is None else (oi, os_, o64, op)
 
 
+def bits_tensor(bits, device):
+    """Label bitsets (numpy uint64 / int64, or a torch int64 tensor carrying the uint64 bits) -> int64 on `device`."""
+    if isinstance(bits, torch.Tensor):
+        return bits.to(device, torch.int64)
+    a = np.ascontiguousarray(bits)
+    return torch.from_numpy(a.view(np.int64) if a.dtype == np.uint64 else a.astype(np.int64)).to(device)
+
+
+def drop_excluded(idx: torch.Tensor, exclude: torch.Tensor):
+    """A ranked list (B, k) searched one longer than needed -> (B, k - 1) without the query's excluded global
+    index, order kept (a list that does not hold it loses its last entry), on the list's device."""
+    hit = idx == exclude.to(idx.device)[:, None]
+    order = torch.argsort(hit.to(torch.int8), dim=1, stable=True)
+    return torch.gather(idx, 1, order)[:, :idx.shape[1] - 1]
+
+
+def list_flags(idx: torch.Tensor, q_bits: torch.Tensor, g_bits: torch.Tensor):
+    """Relevance of a ranked list of global indices (B, k), -1 = empty: gallery_bits[idx] & query_bits != 0."""
+    gb = g_bits[idx.clamp(min=0)]
+    return ((gb & q_bits[:, None]) != 0) & (idx >= 0)
+
+
 def rerank_mix(cand: torch.Tensor, comp: torch.Tensor, topk: int, alpha=0.6, beta=0.25, gamma=0.15,
                want_components=True):
     """After the shard merge (mmr_rerank_mix): cand (nq, kc) global indices (-1 = empty) + their raw
@@ -325,6 +397,36 @@ class MI355XRetrievalEngine(RetrievalEngine):
         if is_np:
             return idx.cpu().numpy(), sc.cpu().numpy()
         return idx, sc
+
+    def exclude_tensor(self, exclude_ids, nq, device):
+        """exclude_ids (gallery row indices, -1 = none, or record ids) -> (nq,) int64 on `device`."""
+        ex = [self.id2idx.get(x, -1) if isinstance(x, str) else int(x) for x in
+              (exclude_ids.tolist() if hasattr(exclude_ids, "tolist") else list(exclude_ids))]
+        if len(ex) != nq:
+            raise ValueError(f"{len(ex)} exclude_ids for {nq} queries")
+        return torch.tensor(ex, dtype=torch.int64, device=device)
+
+    def evaluate(self, Q, query_bits, gallery_bits, ks=(1, 5, 10), exclude_ids=None):
+        """The reference's evaluation of a model's embeddings, exact at any gallery size: compute_ranking_metrics
+        (retrieval_overlap.py:84-115) ranks the WHOLE gallery per query and takes the rank of the first item
+        sharing a label; Helpers/retrieval_metrics.py scores the top-k list.  Q (B, D); query_bits (B,) /
+        gallery_bits (N,) label bitsets (numpy uint64 or device int64); exclude_ids (B,) gallery rows (or record
+        ids) that do not exist for their query, -1 = none (contructGT.py:73 drops the query itself).
+        One search at max(ks) (+ 1 with exclusions, the excluded row dropped on device) and one full-ranking
+        pass (GalleryIndex.rank_eval).  -> metrics.evaluation_summary's dict: `mrr`, `hit@k`, `recall@k`,
+        `p@k`, `map@k`, `ndcg@k`, `mrr@K`, and the per-query `first_rank` / `n_rel` device tensors."""
+        from .metrics import evaluation_summary
+        dev = f"cuda:{self.device}"
+        q = torch.as_tensor(np.asarray(Q, np.float32) if not isinstance(Q, torch.Tensor) else Q).to(dev, torch.float32)
+        qb, gb = bits_tensor(query_bits, dev), bits_tensor(gallery_bits, dev)
+        ex = None if exclude_ids is None else self.exclude_tensor(exclude_ids, q.shape[0], dev)
+        k_eff = min(max(ks) + (0 if ex is None else 1), len(self.ids))
+        idx, _, st = self.index.search(q, k_eff, want_status=True)
+        check_status(st)
+        if ex is not None:
+            idx = drop_excluded(idx, ex)
+        first_rank, n_rel, _, _ = self.index.rank_eval(q, qb, gb, ex)
+        return evaluation_summary(list_flags(idx, qb, gb), first_rank, n_rel, ks)
 
     def retrieve(self, query_emb, K: int = 5, reranker=None, query_id=None, rerank_topk=None, **kwargs):
         """(D,) or (1,D) query -> (top-K ids, scores) descending (retrieval.py:34-39 contract).
