@@ -716,6 +716,30 @@ mmr_status mmr_classifier_head(const float* x, int64_t ldx, const void* images, 
                                int32_t* topk_idx, int32_t b, int32_t d, int32_t h, int32_t c, int32_t k,
                                float threshold, void* stream);
 
+/* ---------------------------------------------------------------- classifier evaluation */
+/* The reference's evaluation of its classifier (src/Evaluate/eval_on_test.py; Trainner/train.py:621-681) on
+ * device, csrc/cls_eval.hip: scores (n, c) f32 rows at stride lds (>= c; probabilities or logits, any finite
+ * values; -0 == +0, denormals are distinct scores), label_bits (n) uint64 (bit j = the sample has class j).
+ * Result rows 0 .. c - 1 are the classes, row c the n * c flattened (score, label) pairs (sklearn's
+ * average='micro').  Per row, with the distinct scores in descending order as tie groups, tp / fp = positives /
+ * negatives scoring >= a group's value, dtp / dfp = the group's own:
+ *   counts (c + 1, 4) int64: n_pos P, n_neg Nn, A = sum over groups of dfp (2 (tp - dtp) + dtp) = 2 #(pos > neg) +
+ *     #(pos == neg) (AUROC = A / (2 P Nn)), the number of distinct scores
+ *   ap_sum (c + 1) f64 = sum over groups of dtp * (tp / (tp + fp)) (AP = ap_sum / P), summed in a fixed order
+ *   best_thr (c + 1) f32, best_f1 (c + 1) f64: _find_best_thresholds — over the distinct scores the maximum of
+ *     f1 = (2 p r) / ((p + r) + 1e-8), p = tp / (tp + fp), r = tp / P (1.0 when P == 0), every operation rounded
+ *     on its own in f64; equal f1: the lowest score
+ *   confusion (c + 1, 3) int64 = tp, fp, fn of `score > threshold` against `thresholds` (c) f32 when given, else
+ *     against best_thr (row c: the sums over the classes)
+ *   nonfinite (1) int64 = the number of NaN / infinite scores; the other outputs are meaningless when it is not 0
+ * 1 <= c <= 64, n >= 1, n * c < 2^31.  work: mmr_cls_eval_work_bytes(n, c) bytes (0: shape not taken) of scratch
+ * owned by the caller, 16-B aligned.  All pointers device, asynchronous on `stream`; integer results and
+ * fixed-order f64 sums only: two runs give identical bytes. */
+int64_t mmr_cls_eval_work_bytes(int64_t n, int32_t c);
+mmr_status mmr_cls_eval(const float* scores, int64_t lds, const uint64_t* label_bits, int64_t n, int32_t c,
+                        const float* thresholds, int64_t* counts, double* ap_sum, float* best_thr, double* best_f1,
+                        int64_t* confusion, int64_t* nonfinite, void* work, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -16,6 +16,9 @@ gallery size, with or without the test -> test protocol's self-exclusion (contru
 `list_metrics` is the id-list metrics above on device tensors: relevance flags of a ranked list +
 the per-query relevant count (recall's and AP's denominator) -> P@k, R@k, AP@k, RR, nDCG@k per query;
 `evaluation_summary` turns those and the first ranks into the evaluation's dict.
+`classification_metrics` / `find_best_thresholds` are the classifier's evaluation
+(src/Evaluate/eval_on_test.py: per-class AUROC, AP, best-F1 thresholds, precision / recall / F1, macro
+and micro aggregates) from the exact sums ops.cls_eval computes on the device.
 """
 import math
 
@@ -143,3 +146,145 @@ def evaluation_summary(rel_flags, first_rank, n_rel, ks):
     out = dict(zip(names, means))
     out["first_rank"], out["n_rel"] = first_rank, n_rel
     return out
+
+
+# ---------------------------------------------------------------- classifier evaluation (eval_on_test.py)
+def label_bits(y_true, num_classes, device):
+    """Labels of N samples -> ((N,) int64 tensor on `device` carrying the uint64 bitsets, a 0-d bool tensor: some
+    dense entry was not 0 / 1).  y_true: (N, C) array / tensor of {0, 1}, or (N,) bitsets (numpy uint64 / int64
+    or a torch int64 tensor, as retrieval.bits_tensor takes them)."""
+    C = int(num_classes)
+    if not 1 <= C <= 64:
+        raise ValueError(f"{C} classes outside 1..64 (label sets are uint64 bitsets)")
+    t = y_true if isinstance(y_true, torch.Tensor) else None
+    if t is None:
+        a = np.asarray(y_true)
+        if a.ndim == 1:
+            a = np.ascontiguousarray(a)
+            a = a.view(np.int64) if a.dtype == np.uint64 else a.astype(np.int64)
+        elif a.dtype == np.uint64 or a.dtype == object:
+            a = a.astype(np.int64)
+        a = np.ascontiguousarray(a)
+        t = torch.from_numpy(a if a.flags.writeable else a.copy())
+    t = t.to(device)
+    if t.dim() == 1:
+        return t.to(torch.int64), torch.zeros((), dtype=torch.bool, device=t.device)
+    if t.dim() != 2 or t.shape[1] != C:
+        raise ValueError(f"labels must be (N, {C}) of 0 / 1 or (N,) bitsets, got {tuple(t.shape)}")
+    one = t != 0
+    bad = (one & (t != 1)).any()
+    shifts = torch.arange(C, dtype=torch.int64, device=t.device)
+    # disjoint bits: the sum is the bitwise or (bit 63 wraps into the sign bit, which is the uint64's top bit)
+    return torch.bitwise_left_shift(one.to(torch.int64), shifts[None, :]).sum(dim=1), bad
+
+
+def _scores_tensor(y_score, device=None):
+    if isinstance(y_score, torch.Tensor):
+        t = y_score if y_score.is_cuda or device is None else y_score.to(device)
+        t = t if t.is_cuda else t.to("cuda")
+    else:
+        a = np.ascontiguousarray(np.asarray(y_score, dtype=np.float32))
+        t = torch.from_numpy(a if a.flags.writeable else a.copy()).to(device or "cuda")
+    if t.dim() != 2:
+        raise ValueError(f"scores must be (N, C), got {tuple(t.shape)}")
+    return t.to(torch.float32)
+
+
+def _safe_div(num, den):
+    """num / den in f64, 0 where den == 0 (sklearn's zero_division=0)."""
+    num, den = np.asarray(num, np.float64), np.asarray(den, np.float64)
+    return np.divide(num, den, out=np.zeros(np.broadcast(num, den).shape), where=den != 0)
+
+
+def _nanmean(v):
+    v = np.asarray(v, np.float64)
+    ok = ~np.isnan(v)
+    return float(v[ok].mean()) if ok.any() else float("nan")
+
+
+def classification_metrics(y_true, y_score, thresholds=None, label_names=None):
+    """eval_on_test's metrics dict (src/Evaluate/eval_on_test.py:130-207; Trainner/train.py:621-681), computed on
+    the device by ops.cls_eval (csrc/cls_eval.hip) and derived in f64 from its integer outputs with one host sync.
+
+    y_score (N, C): probabilities or logits, numpy or torch (taken as float32, as the reference's sigmoid
+    outputs are; moved to the GPU when not there); y_true: (N, C) of {0, 1}, or (N,) uint64 label bitsets.
+    thresholds: None — the per-class best-F1 thresholds of _find_best_thresholds (precision_recall_curve's
+    thresholds, f1 = 2 p r / (p + r + 1e-8), argmax, i.e. the lowest score among equal f1) — or a scalar / (C,)
+    vector of fixed ones (use_fixed_threshold).  Predictions are `score > threshold`.
+    -> num_samples, num_classes, macro_auc, macro_ap (nanmean over classes; a class without positives or without
+    negatives is NaN: safe_roc_auc / safe_avg_precision), macro_f1 / macro_prec / macro_rec (mean over classes,
+    zero_division=0), micro_prec / micro_rec / micro_f1 (summed counts), micro_ap (AP of the N C flattened pairs),
+    per_class: labels, auroc, ap, prec, rec, f1, thresholds (lists of float), n_pos (list of int).
+    A NaN / infinite score raises ValueError, as sklearn does."""
+    from . import ops
+    s = _scores_tensor(y_score)
+    N, C = (int(v) for v in s.shape)
+    if label_names is not None and len(label_names) != C:
+        raise ValueError(f"label_names has {len(label_names)} entries for {C} classes")
+    if len(y_true) != N:
+        raise ValueError(f"labels of {len(y_true)} samples for {N} score rows")
+    fixed = None
+    if thresholds is not None:
+        t = thresholds.detach().cpu().numpy() if isinstance(thresholds, torch.Tensor) else np.asarray(thresholds)
+        t = t.astype(np.float32)
+        if t.ndim == 0:
+            t = np.full((C,), t, np.float32)
+        if t.shape != (C,):
+            raise ValueError(f"thresholds must be a scalar or have shape ({C},), got {t.shape}")
+        if not np.isfinite(t).all():
+            raise ValueError("thresholds must be finite")
+        fixed = torch.from_numpy(t)
+    bits, bad = label_bits(y_true, C, s.device)
+    r = ops.cls_eval(s, bits, C, fixed)
+    words = torch.cat([r["counts"].flatten(), r["confusion"].flatten(), r["nonfinite"], r["ap_sum"].view(torch.int64),
+                       r["best_f1"].view(torch.int64), r["best_thr"].view(torch.int32).to(torch.int64),
+                       bad.to(torch.int64).reshape(1)]).cpu().numpy()  # the one host sync
+    R = C + 1
+    o = np.cumsum([0, 4 * R, 3 * R, 1, R, R, R, 1])
+    counts, conf = words[o[0]:o[1]].reshape(R, 4), words[o[1]:o[2]].reshape(R, 3)
+    if words[o[2]] != 0:
+        raise ValueError(f"classification_metrics: {int(words[o[2]])} scores are NaN or infinite")
+    if words[o[6]] != 0:
+        raise ValueError("classification_metrics: labels must be 0 or 1")
+    ap_sum = words[o[3]:o[4]].copy().view(np.float64)
+    best_thr = words[o[5]:o[6]].astype(np.int32).view(np.float32)
+    n_pos, n_neg, A = counts[:, 0], counts[:, 1], counts[:, 2]
+    both = (n_pos > 0) & (n_neg > 0)
+    nan = np.full(R, np.nan)
+    auroc = np.divide(A.astype(np.float64), (2 * n_pos * n_neg).astype(np.float64), out=nan.copy(), where=both)
+    ap = np.divide(ap_sum, n_pos.astype(np.float64), out=nan.copy(), where=both)
+    thr = fixed.numpy() if fixed is not None else best_thr[:C]
+    tp, fp, fn = conf[:C, 0], conf[:C, 1], conf[:C, 2]
+    prec, rec, f1 = _safe_div(tp, tp + fp), _safe_div(tp, tp + fn), _safe_div(2 * tp, 2 * tp + fp + fn)
+    TP, FP, FN = (int(v) for v in conf[C])
+    # micro AP: only "no positives at all" is undefined (sklearn: 0 with a warning; kept as 0)
+    micro_ap = float(ap_sum[C] / n_pos[C]) if n_pos[C] > 0 else 0.0
+    return {
+        "num_samples": N, "num_classes": C,
+        "macro_auc": _nanmean(auroc[:C]), "macro_ap": _nanmean(ap[:C]), "macro_f1": float(f1.mean()),
+        "micro_ap": micro_ap, "micro_f1": float(_safe_div(2 * TP, 2 * TP + FP + FN)),
+        "macro_prec": float(prec.mean()), "macro_rec": float(rec.mean()),
+        "micro_prec": float(_safe_div(TP, TP + FP)), "micro_rec": float(_safe_div(TP, TP + FN)),
+        "per_class": {"labels": list(label_names) if label_names is not None else list(range(C)),
+                      "auroc": [float(x) for x in auroc[:C]], "ap": [float(x) for x in ap[:C]],
+                      "prec": [float(x) for x in prec], "rec": [float(x) for x in rec], "f1": [float(x) for x in f1],
+                      "thresholds": [float(x) for x in thr], "n_pos": [int(x) for x in n_pos[:C]]},
+    }
+
+
+def find_best_thresholds(y_true, y_score):
+    """_find_best_thresholds (eval_on_test.py:29-38; retrieval_overlap.py:40-49) on the device: per class the
+    lowest score with the maximal f1 = 2 p r / (p + r + 1e-8) over precision_recall_curve's thresholds -> (C,)
+    float32 (a class without positives gets its minimum score, as there)."""
+    from . import ops
+    s = _scores_tensor(y_score)
+    C = int(s.shape[1])
+    bits, bad = label_bits(y_true, C, s.device)
+    r = ops.cls_eval(s, bits, C)
+    flags = torch.cat([r["nonfinite"], bad.to(torch.int64).reshape(1)])
+    thr, flags = r["best_thr"][:C].cpu().numpy(), flags.cpu().numpy()
+    if flags[0] != 0:
+        raise ValueError(f"find_best_thresholds: {int(flags[0])} scores are NaN or infinite")
+    if flags[1] != 0:
+        raise ValueError("find_best_thresholds: labels must be 0 or 1")
+    return thr

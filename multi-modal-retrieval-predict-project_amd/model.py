@@ -31,9 +31,10 @@ import json
 import os
 from pathlib import Path
 
+import numpy as np
 import torch
 
-from . import ops
+from . import metrics, ops
 from .fusion import FusionStack
 from .towers import BERT_BASE, SWIN_T, SWIN_ARCHS, BertTower, SwinTower, init_bert_state, init_swin_state
 from .towers_x3 import BertTowerX3, SwinTowerX3
@@ -395,9 +396,21 @@ class MultiModalRetrievalModel:
             raise ValueError("predict needs classifier.0.* / classifier.3.* weights in the checkpoint / head_state")
         if retrieve and self.retriever is None:
             raise ValueError("predict(retrieve=True) needs a retriever (set_retriever / retriever=)")
+        thr_vec = None
+        if isinstance(threshold, (torch.Tensor, np.ndarray, list, tuple)) and np.ndim(threshold) > 0:
+            # per-class thresholds (the reference's `probs >= threshold` broadcasts, e.g. best_ts of
+            # metrics.find_best_thresholds): compared with the kernel's probs here, the kernel's scalar left alone
+            thr_vec = torch.as_tensor(threshold).detach().to(device=self.device, dtype=torch.float32)
+            if tuple(thr_vec.shape) != (self.classifier.c,):
+                raise ValueError(f"predict: threshold must be a scalar or have shape ({self.classifier.c},), got "
+                                 f"{tuple(thr_vec.shape)}")
         joint = self._forward(image, input_ids, attention_mask)["joint_emb"]
-        res = ops.classifier_head(joint, self.classifier, k=K, threshold=threshold,
-                                  want=("probs", "preds", "topk_vals", "topk_idx"))
+        if thr_vec is None:
+            res = ops.classifier_head(joint, self.classifier, k=K, threshold=threshold,
+                                      want=("probs", "preds", "topk_vals", "topk_idx"))
+        else:
+            res = ops.classifier_head(joint, self.classifier, k=K, want=("probs", "topk_vals", "topk_idx"))
+            res["preds"] = (res["probs"] >= thr_vec[None, :]).to(torch.int32)
         output = {"probs": res["probs"].cpu().numpy(), "preds": res["preds"].cpu().numpy(),
                   "topk_idx": res["topk_idx"].cpu().tolist(), "topk_vals": res["topk_vals"].cpu().tolist()}
         if retrieve:
@@ -408,6 +421,43 @@ class MultiModalRetrievalModel:
                 dists.append(d)
             output["retrieval_ids"], output["retrieval_dists"] = ids, dists
         return output
+
+    def evaluate_classifier(self, batches, thresholds=None, return_outputs=False):
+        """eval_on_test (src/Evaluate/eval_on_test.py:103-207) over `batches`, an iterable of (image, input_ids,
+        attention_mask, labels) with labels (B, C) of {0, 1} or (B,) uint64 bitsets: one forward and one
+        ops.classifier_head(want=("probs",)) per batch, the probabilities kept on the device, then ONE
+        metrics.classification_metrics call -> its dict (per-class AUROC / AP / precision / recall / F1 at the
+        per-class best-F1 thresholds, or at `thresholds` — a scalar or (C,) — when given, and the macro / micro
+        aggregates).  return_outputs=True adds the detailed CSV's columns: "probs" (N, C) float32, "preds" (N, C)
+        int32 = probs > thresholds, "labels" (N, C) int32."""
+        if self.classifier is None:
+            raise ValueError("predict needs classifier.0.* / classifier.3.* weights in the checkpoint / head_state")
+        C = self.classifier.c
+
+        def dev(t):
+            return t.to(self.device) if isinstance(t, torch.Tensor) else t
+        probs, bits, bad = [], [], []
+        for image, input_ids, attention_mask, labels in batches:
+            joint = self._forward(dev(image), dev(input_ids), dev(attention_mask))["joint_emb"]
+            probs.append(ops.classifier_head(joint, self.classifier, want=("probs",))["probs"])
+            b, flag = metrics.label_bits(labels, C, self.device)
+            if b.shape[0] != joint.shape[0]:
+                raise ValueError(f"evaluate_classifier: {b.shape[0]} label rows for a batch of {joint.shape[0]}")
+            bits.append(b)
+            bad.append(flag)
+        if not probs:
+            raise RuntimeError("evaluate_classifier: no batches")  # eval_on_test.py:124
+        if bool(torch.stack(bad).any()):
+            raise ValueError("evaluate_classifier: labels must be 0 or 1")
+        probs, bits = torch.cat(probs), torch.cat(bits)
+        out = metrics.classification_metrics(bits, probs, thresholds=thresholds)
+        if return_outputs:
+            thr = np.asarray(out["per_class"]["thresholds"], np.float32)
+            p = probs.cpu().numpy()
+            shifts = torch.arange(C, dtype=torch.int64, device=bits.device)
+            out["probs"], out["preds"] = p, (p > thr[None, :]).astype(np.int32)
+            out["labels"] = ((bits[:, None] >> shifts[None, :]) & 1).to(torch.int32).cpu().numpy()
+        return out
 
     def query_embeddings(self, image, input_ids, attention_mask):
         """Retrieval keys of one batch.  multimodal: (B, D) f32 joint embeddings of (image, report)

@@ -549,6 +549,60 @@ def classifier_head(x, cw, k=None, threshold=0.5, want=("logits",), out=None):
     return {name: res[name] for name in want}
 
 
+CLS_EVAL_MAX_CLASSES = 64  # label sets are uint64 bitsets
+
+
+def cls_eval(scores, label_bits, num_classes, thresholds=None):
+    """The classifier evaluation's exact sums in one mmr_cls_eval call (csrc/cls_eval.hip; eval_on_test.py):
+    scores (N, C) f32 device rows (unit column stride, any row stride >= C; probabilities or logits), label_bits
+    (N,) int64 carrying the uint64 label bitsets (retrieval.bits_tensor), thresholds None (the best-F1
+    thresholds are used for the confusion counts) or (C,) f32.  -> dict of device tensors, rows 0 .. C - 1 the
+    classes and row C the N * C flattened pairs (micro):
+      counts (C + 1, 4) int64 = n_pos, n_neg, A (AUROC = A / (2 n_pos n_neg)), n_distinct scores
+      ap_sum (C + 1,) f64 (AP = ap_sum / n_pos);  best_thr (C + 1,) f32, best_f1 (C + 1,) f64
+      confusion (C + 1, 3) int64 = tp, fp, fn of scores > threshold;  nonfinite (1,) int64.
+    Nothing is synchronised: a NaN / infinite score shows in `nonfinite` (the other outputs are then undefined)."""
+    _lib.require_gpu(scores)
+    if scores.dim() != 2 or scores.dtype != torch.float32:
+        raise ValueError(f"cls_eval: scores must be (N, C) float32, got {tuple(scores.shape)} {scores.dtype}")
+    N, C = (int(s) for s in scores.shape)
+    if C != int(num_classes):
+        raise ValueError(f"cls_eval: scores have {C} columns, num_classes is {num_classes}")
+    if not 1 <= C <= CLS_EVAL_MAX_CLASSES:
+        raise ValueError(f"cls_eval: {C} classes outside 1..{CLS_EVAL_MAX_CLASSES} (label sets are uint64 bitsets)")
+    if N < 1:
+        raise ValueError("cls_eval: no samples")
+    if N * C >= 2 ** 31:
+        raise ValueError(f"cls_eval: N * C = {N} * {C} >= 2^31")
+    if (C > 1 and scores.stride(1) != 1) or (N > 1 and scores.stride(0) < C):
+        scores = scores.contiguous()
+    lds = scores.stride(0) if N > 1 else C
+    if label_bits.dim() != 1 or label_bits.shape[0] != N or label_bits.dtype != torch.int64:
+        raise ValueError(f"cls_eval: label_bits must be ({N},) int64 bitsets, got {tuple(label_bits.shape)} "
+                         f"{label_bits.dtype}")
+    dev = scores.device
+    label_bits = label_bits.to(dev).contiguous()
+    if thresholds is not None:
+        if tuple(thresholds.shape) != (C,):
+            raise ValueError(f"cls_eval: thresholds must have shape ({C},), got {tuple(thresholds.shape)}")
+        thresholds = thresholds.to(device=dev, dtype=torch.float32).contiguous()
+    res = {"counts": torch.empty((C + 1, 4), dtype=torch.int64, device=dev),
+           "ap_sum": torch.empty((C + 1,), dtype=torch.float64, device=dev),
+           "best_thr": torch.empty((C + 1,), dtype=torch.float32, device=dev),
+           "best_f1": torch.empty((C + 1,), dtype=torch.float64, device=dev),
+           "confusion": torch.empty((C + 1, 3), dtype=torch.int64, device=dev),
+           "nonfinite": torch.empty((1,), dtype=torch.int64, device=dev)}
+    nwork = int(_L().mmr_cls_eval_work_bytes(N, C))
+    if nwork <= 0:
+        raise ValueError(f"cls_eval: shape ({N}, {C}) is not taken")
+    work = torch.empty(nwork, dtype=torch.uint8, device=dev)
+    _chk(_L().mmr_cls_eval(_lib.ptr(scores), lds, _lib.ptr(label_bits), N, C, _lib.ptr(thresholds),
+                           _lib.ptr(res["counts"]), _lib.ptr(res["ap_sum"]), _lib.ptr(res["best_thr"]),
+                           _lib.ptr(res["best_f1"]), _lib.ptr(res["confusion"]), _lib.ptr(res["nonfinite"]),
+                           _lib.ptr(work), _s(scores)), "mmr_cls_eval")
+    return res
+
+
 def mha(q, k, v, b, lq, lk, heads, dh, scale, out=None, mean_out=None, q8=False):
     """Attention core over strided row views: q (b*lq, >=heads*dh) etc. (unit column stride).  q8: the
     output also as an MX-fp8 activation operand, returned as (out, mean_out, MXFP8)."""
