@@ -28,8 +28,10 @@
 
 namespace {
 
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
+using mmr::aligned16;
+using mmr::bf16x8;
+using mmr::f32x16;
+using mmr::LGKM0;
 
 constexpr int AP_KB = 64;           // keys per pass-B block: two 32-key MFMA tiles
 constexpr int AP_TROW = AP_KB + 1;  // floats per row of the transpose tile (odd: the column writes spread over banks)
@@ -50,7 +52,9 @@ struct ProbArgs {
 
 constexpr size_t ap_wave_lds(int heads) { return (size_t)heads * 32 * 8 + (size_t)32 * AP_TROW * 4; }
 
-// f32 x8 -> (hi, lo) bf16 x8 (x3.hip split8)
+// f32 x8 -> (hi, lo) bf16 x8: mmr::split8's arithmetic with all four hi words formed first.  Kept apart from it:
+// on mmr::split8 attn_probs<2, true> goes from 178 to 148 VGPRs (tools/isa_diff.py), 2 -> 3 waves per SIMD, and
+// no timer reaches these kernels to say what that does to them
 __device__ __forceinline__ void split8(const float4 a, const float4 b, bf16x8& hi, bf16x8& lo) {
   const uint32_t h0 = mmr::pack2bf(a.x, a.y), h1 = mmr::pack2bf(a.z, a.w);
   const uint32_t h2 = mmr::pack2bf(b.x, b.y), h3 = mmr::pack2bf(b.z, b.w);
@@ -122,7 +126,7 @@ __device__ __forceinline__ f32x16 score_tile(const ProbArgs& a, int64_t kbase, i
 
 // this wave's LDS writes landed and visible to its other lanes (the LDS regions are wave-private)
 __device__ __forceinline__ void wave_lds_sync() {
-  __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0)
+  __builtin_amdgcn_s_waitcnt(LGKM0);  // lgkmcnt(0)
   __builtin_amdgcn_wave_barrier();
 }
 
@@ -197,8 +201,6 @@ __global__ __launch_bounds__(256) void attn_probs(const ProbArgs a) {
   }
 }
 
-bool al16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
-
 template <bool X3>
 mmr_status launch_probs(const char* who, const void* q, int64_t ldq, const void* k, int64_t ldk, float* probs,
                         int64_t ldp, int32_t b, int32_t lq, int32_t lk, int32_t heads, int32_t dh, float scale,
@@ -208,7 +210,7 @@ mmr_status launch_probs(const char* who, const void* q, int64_t ldq, const void*
   MMR_REQUIRE(b >= 0 && lq > 0 && lk > 0 && heads > 0 && dh > 0 && dh % 8 == 0 && dh <= MAXDH,
               "%s: bad shape b=%d lq=%d lk=%d heads=%d head_dim %d (head_dim %% 8 == 0, <= %d)", who, b, lq, lk, heads,
               dh, MAXDH);
-  MMR_REQUIRE(ldq % AL == 0 && ldk % AL == 0 && al16(q) && al16(k) && (int64_t)heads * dh <= ldq &&
+  MMR_REQUIRE(ldq % AL == 0 && ldk % AL == 0 && aligned16(q) && aligned16(k) && (int64_t)heads * dh <= ldq &&
                   (int64_t)heads * dh <= ldk,
               "%s: q / k rows must be 16-B aligned with strides >= heads*dh", who);
   MMR_REQUIRE(ldp >= lk && ((uintptr_t)probs & 3u) == 0, "%s: ldp=%lld below lk=%d (or probs misaligned)", who,

@@ -21,6 +21,17 @@ std::atomic<int> pin_gemm_bf16{-1};
 std::atomic<int> pin_x3_waves{-1};
 std::atomic<int> pin_x3_mlp{-1};
 std::atomic<int> pin_swa{-1};
+
+int cu_count() {
+  static int n = [] {
+    int dev = 0, v = 0;
+    if (hipGetDevice(&dev) != hipSuccess ||
+        hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0)
+      v = 256;
+    return v;
+  }();
+  return n;
+}
 }  // namespace mmr
 
 extern "C" {

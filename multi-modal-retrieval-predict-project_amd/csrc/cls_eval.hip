@@ -42,6 +42,8 @@
 
 namespace {
 
+using mmr::aligned16;
+
 constexpr int CE_WMAX = 4096;  // sort chunks (waves) per pass at most
 constexpr int CE_TILE = 1024;  // curve tile: 256 threads x 4 consecutive keys
 constexpr int CE_MAXC = 64;
@@ -541,7 +543,7 @@ mmr_status mmr_cls_eval(const float* scores, int64_t lds, const uint64_t* label_
   MMR_REQUIRE(lds >= c, "mmr_cls_eval: row stride %lld < c = %d", (long long)lds, c);
   MMR_REQUIRE(scores && label_bits, "mmr_cls_eval: NULL scores / label_bits");
   MMR_REQUIRE(counts && ap_sum && best_thr && best_f1 && confusion && nonfinite, "mmr_cls_eval: NULL output");
-  MMR_REQUIRE(work && ((uintptr_t)work & 15u) == 0, "mmr_cls_eval: work is NULL or not 16-B aligned");
+  MMR_REQUIRE(work && aligned16(work), "mmr_cls_eval: work is NULL or not 16-B aligned");
   hipStream_t st = mmr::as_stream(stream);
   const int64_t m = n * c;
   const CeWork w = ce_layout(n, c, work);

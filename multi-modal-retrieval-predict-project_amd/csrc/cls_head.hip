@@ -24,9 +24,11 @@
 
 namespace {
 
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+using mmr::aligned16;
+using mmr::bf16x8;
+using mmr::f32x16;
+using mmr::f32x4;
+using mmr::split2;
 
 constexpr int CLS_MAX_C = 256;
 enum { CLS_NONE = -1, CLS_FUSED = 0, CLS_CHAIN_X3 = 1, CLS_CHAIN_F32 = 2 };
@@ -46,12 +48,6 @@ inline int cls_route(int d, int h, int c) {
 inline int cls_slab_tiles(int d) { return (d / 128) % 3 == 0 ? 3 : 4; }
 inline int cls_slabs(int d) { return d / 8 / cls_slab_tiles(d); }
 inline int64_t cls_part_bytes(int64_t b, int cp) { return mmr::round_up(b * cp * 4, 256); }
-
-// two f32 -> (hi, lo) packed bf16 pairs
-__device__ __forceinline__ void split2(float a, float b, uint32_t& hi, uint32_t& lo) {
-  hi = mmr::pack2bf(a, b);
-  lo = mmr::pack2bf(a - __uint_as_float(hi << 16), b - __uint_as_float(hi & 0xFFFF0000u));
-}
 
 // Fused images, both in MFMA A-fragment order (fragment = [hi 64 lanes x 8 | lo 64 lanes x 8] bf16, lane
 // (r, hf) = (lane % 32, lane / 32)):
@@ -317,7 +313,7 @@ mmr_status mmr_classifier_pack(const float* w1, const float* w2, void* images, i
   mmr::clear_error();
   MMR_REQUIRE(w1 && w2 && images, "mmr_classifier_pack: NULL pointer");
   MMR_REQUIRE(d > 0 && h > 0 && c >= 1, "mmr_classifier_pack: d=%d h=%d c=%d", d, h, c);
-  MMR_REQUIRE(((uintptr_t)images & 15u) == 0, "mmr_classifier_pack: images must be 16-B aligned");
+  MMR_REQUIRE(aligned16(images), "mmr_classifier_pack: images must be 16-B aligned");
   const int route = cls_route(d, h, c);
   if (route == CLS_NONE) {
     mmr::set_error("mmr_classifier_pack: d=%d h=%d c=%d not built (c <= %d; d %% 16 == 0, h %% 32 == 0)", d, h, c,
@@ -369,8 +365,8 @@ mmr_status mmr_classifier_head(const float* x, int64_t ldx, const void* images, 
     return MMR_ERR_UNSUPPORTED;
   }
   MMR_REQUIRE(ldx >= d && ldx % 4 == 0, "mmr_classifier_head: ldx=%lld (>= d, %% 4 == 0)", (long long)ldx);
-  auto al = [](const void* p) { return ((uintptr_t)p & 15u) == 0; };
-  MMR_REQUIRE(al(x) && al(images) && al(b1) && al(work), "mmr_classifier_head: x / images / b1 / work 16-B aligned");
+  MMR_REQUIRE(aligned16(x) && aligned16(images) && aligned16(b1) && aligned16(work),
+              "mmr_classifier_head: x / images / b1 / work 16-B aligned");
   if (b == 0) return MMR_OK;
   hipStream_t st = mmr::as_stream(stream);
   const int cp = cls_cp(c);

@@ -36,6 +36,38 @@ inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s);
 __host__ __device__ inline int64_t round_up(int64_t x, int64_t m) { return (x + m - 1) / m * m; }
 __host__ __device__ inline int64_t ceil_div(int64_t x, int64_t m) { return (x + m - 1) / m; }
 
+// CUs of the current device (queried once; 256 where the query fails): the persistent kernels' grid size
+int cu_count();
+
+// makes `dev` the current device for a scope
+struct DeviceGuard {
+  int prev = -1;
+  explicit DeviceGuard(int dev) {
+    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
+    if (prev != dev) (void)hipSetDevice(dev);
+  }
+  ~DeviceGuard() {
+    if (prev >= 0) (void)hipSetDevice(prev);
+  }
+};
+
+inline bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
+
+// MFMA operand / accumulator and wide load / store vectors (bf16 as bit patterns)
+typedef short bf16x8 __attribute__((ext_vector_type(8)));
+typedef short bf16x4 __attribute__((ext_vector_type(4)));
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+
+// s_waitcnt immediates (gfx9: vmcnt in bits 3:0 and 15:14, expcnt 6:4, lgkmcnt 11:8; a field at its maximum
+// is not waited for): vmcnt(n) alone, and lgkmcnt(0) alone — LDS, scalar-memory and message operations done
+constexpr int vmcnt_n(int n) { return (n & 15) | (7 << 4) | (15 << 8) | ((n >> 4) << 14); }
+constexpr int LGKM0 = 0xC07F;
+
 // blockIdx -> work index such that the blocks the dispatcher places on one XCD (orig % 8) get a
 // contiguous run of work indices (bijective for any n): neighbouring work units — the heads of
 // one batch row, sharing 128-B lines of a fused QKV row — then meet in the same XCD's L2.
@@ -93,6 +125,45 @@ __device__ __forceinline__ uint32_t pack2bf(float a, float b) {
   return __builtin_bit_cast(uint32_t, v);
 }
 
+// bf16x3 (the x3 tower mode, x3.hip): a = a_hi + a_lo with a_hi = bf16(a), a_lo = bf16(a - a_hi), and
+// a.b ~= a_hi.b_hi + a_hi.b_lo + a_lo.b_hi accumulated in f32.
+// two f32 -> (hi, lo) packed bf16 pairs
+__device__ __forceinline__ void split2(float a, float b, uint32_t& hi, uint32_t& lo) {
+  hi = mmr::pack2bf(a, b);
+  lo = mmr::pack2bf(a - __uint_as_float(hi << 16), b - __uint_as_float(hi & 0xFFFF0000u));
+}
+// f32 x8 -> the (hi, lo) MFMA operands.  x3.hip, attn_probs.hip and x3_sab.hip keep spellings of their own with the
+// statements in another order: hipcc's schedule, and in x3_sab.hip its fma contraction, follow that order (see there)
+__device__ __forceinline__ void split8(const float4 a, const float4 b, bf16x8& hi, bf16x8& lo) {
+  uint32_t h[4], l[4];
+  split2(a.x, a.y, h[0], l[0]);
+  split2(a.z, a.w, h[1], l[1]);
+  split2(b.x, b.y, h[2], l[2]);
+  split2(b.z, b.w, h[3], l[3]);
+  hi = __builtin_bit_cast(bf16x8, make_uint4(h[0], h[1], h[2], h[3]));
+  lo = __builtin_bit_cast(bf16x8, make_uint4(l[0], l[1], l[2], l[3]));
+}
+__device__ __forceinline__ f32x4 mfma3(const bf16x8 ah, const bf16x8 al, const bf16x8 bh, const bf16x8 bl, f32x4 acc) {
+  acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bh, acc, 0, 0, 0);
+  acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bl, acc, 0, 0, 0);
+  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(al, bh, acc, 0, 0, 0);
+}
+__device__ __forceinline__ f32x16 mfma3(const bf16x8 ah, const bf16x8 al, const bf16x8 bh, const bf16x8 bl, f32x16 c) {
+  c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh, c, 0, 0, 0);
+  c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl, c, 0, 0, 0);
+  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh, c, 0, 0, 0);
+}
+
+// reductions across the two lane halves (lane l and l ^ 32): v_permlane32_swap, no LDS round trip
+__device__ __forceinline__ float half_sum(float v) {
+  const auto p = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
+  return __uint_as_float(p[0]) + __uint_as_float(p[1]);
+}
+__device__ __forceinline__ float half_max(float v) {
+  const auto p = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
+  return fmaxf(__uint_as_float(p[0]), __uint_as_float(p[1]));
+}
+
 // e^x for the x3 softmax (x = s - max <= 0; -inf is the caller's case): 2^t with t = RN(x log2 e) and t's
 // rounding error carried to first order, 2^t (1 + ln 2 (fma(x, L2E, -t) + x L2E_lo)) — one v_exp_f32
 // (1 ulp) and four FMA-class ops, <= ~2 ulp, against ocml expf's ~14 VALU (range reduction by rndne /
@@ -109,7 +180,10 @@ __device__ __forceinline__ float exp_acc(float x) {
 }
 
 // GELU(erf) with erf from Abramowitz-Stegun 7.1.26 (|err| <= 1.5e-7): branch-free, one exp + one
-// rcp instead of ocml's erff.
+// rcp instead of ocml's erff.  The x3 mode's GELU as well: its absolute error <= 0.75e-7 |x| is 100x below the
+// bf16x3 products' 2^-17, and ocml erff (a branchy polynomial) made the fused x3 MLP VALU-bound: stage 1 615 vs
+// 529 us, stage 2 587 vs 464 us at B = 256, the same max deviation from the unfused chain
+// (profiles/r05_x3_mlp_ab.txt).
 __device__ __forceinline__ float erf_as(float x) {
   const float a = fabsf(x);
   const float t = __builtin_amdgcn_rcpf(fmaf(0.3275911f, a, 1.0f));  // v_rcp_f32 (1 ulp), not a division

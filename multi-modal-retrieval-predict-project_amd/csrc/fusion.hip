@@ -13,12 +13,13 @@
 
 namespace {
 
+using mmr::aligned16;
+using mmr::bf16x4;
+using mmr::bf16x8;
 using mmr::bf2f;
 using mmr::f2bf;
-
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
-typedef short bf16x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
+using mmr::f32x16;
+using mmr::LGKM0;
 
 // ------------------------------------------------------------------ small-sequence MHA core
 // softmax(q k^T * scale) v per (batch, head): the fusion's short sequences (text L <= 512,
@@ -288,7 +289,7 @@ __global__ __launch_bounds__(256, DT == 1 ? 4 : (DT <= 3 ? 3 : 2)) void mha_smal
           w.y = mmr::pack2bf(o[dt][4 * g4 + 2] * inv, o[dt][4 * g4 + 3] * inv);
           *(uint2*)(st + r * OROW + d) = w;
         }
-      __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0): this wave's LDS writes landed
+      __builtin_amdgcn_s_waitcnt(LGKM0);  // lgkmcnt(0): this wave's LDS writes landed
       __builtin_amdgcn_wave_barrier();
       const int nc4 = dh / 4;
       if (out != nullptr)
@@ -329,7 +330,7 @@ __global__ __launch_bounds__(256, DT == 1 ? 4 : (DT <= 3 ? 3 : 2)) void mha_smal
           }
         }
       }
-      __builtin_amdgcn_s_waitcnt(0xC07F);
+      __builtin_amdgcn_s_waitcnt(LGKM0);
       __builtin_amdgcn_wave_barrier();
     }
     if (mean_out != nullptr) {
@@ -340,7 +341,7 @@ __global__ __launch_bounds__(256, DT == 1 ? 4 : (DT <= 3 ? 3 : 2)) void mha_smal
           const int d = dt * 32 + (rg & 3) + 8 * (rg >> 2) + 4 * hf;
           red[d * RLD + r] = qok ? o[dt][rg] * inv : 0.f;
         }
-      __builtin_amdgcn_s_waitcnt(0xC07F);
+      __builtin_amdgcn_s_waitcnt(LGKM0);
       __builtin_amdgcn_wave_barrier();
       for (int d = lane; d < DHP; d += 64) {
         float acc = 0.f;
@@ -775,8 +776,6 @@ __global__ __launch_bounds__(256) void rows_to_f32(const uint16_t* __restrict__ 
   y[i] = bf2f(x[(i / c) * ldx + (i % c)]);
 }
 
-bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
-
 mmr_status launch_mha(const char* who, const uint16_t* q, int64_t ldq, const uint16_t* k, int64_t ldk,
                       const uint16_t* v, int64_t ldv, uint16_t* out, int64_t ldo, float* mean_out,
                       const int64_t* kmask, int32_t b, int32_t lq, int32_t lk, int32_t heads, int32_t dh,
@@ -971,7 +970,7 @@ mmr_status mmr_ln_rows_split(const float* x, int64_t ldx, const float* alpha, co
   mmr::clear_error();
   MMR_REQUIRE(x && gamma && beta && xs && rows >= 0 && c > 0 && c % 4 == 0 && c <= 1024,
               "mmr_ln_rows_split: bad arguments (c %% 4 == 0, c <= 1024; rows=%lld c=%d)", (long long)rows, c);
-  auto al = [](const void* p, int64_t ld) { return p == nullptr || (((uintptr_t)p & 15) == 0 && ld % 4 == 0); };
+  auto al = [](const void* p, int64_t ld) { return p == nullptr || (aligned16(p) && ld % 4 == 0); };
   MMR_REQUIRE(al(x, ldx) && al(residual, ldr) && al(y, ldy) && al(gamma, 0) && al(beta, 0) && al(xs, 0),
               "mmr_ln_rows_split: rows / parameters must be 16-B aligned (row strides multiples of 4)");
   if (rows == 0) return MMR_OK;

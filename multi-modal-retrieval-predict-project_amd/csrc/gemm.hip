@@ -29,8 +29,15 @@
 
 namespace {
 
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+using mmr::aligned16;
+using mmr::bf16x8;
+using mmr::cu_count;
+using mmr::f16x8;
+using mmr::f32x4;
+using mmr::LGKM0;
+using mmr::u32x2;
+using mmr::u32x4;
+using mmr::vmcnt_n;
 typedef int i32x4_t __attribute__((ext_vector_type(4)));
 
 constexpr int BM = 128, BN = 128, BK = 64;
@@ -155,7 +162,7 @@ __global__ __launch_bounds__(256, 2) void gemm_bf16_tn(const uint16_t* __restric
       *(uint2*)(et + (i * 16 + fr) * EPI_LD + nl) = pk;
     }
   }
-  __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0): this wave's LDS writes landed
+  __builtin_amdgcn_s_waitcnt(LGKM0);  // lgkmcnt(0): this wave's LDS writes landed
   __builtin_amdgcn_wave_barrier();
 #pragma unroll
   for (int it = 0; it < 8; ++it) {
@@ -185,7 +192,6 @@ __global__ __launch_bounds__(256, 2) void gemm_bf16_tn(const uint16_t* __restric
 // a STAGES-deep LDS ring filled by glds (source-swizzled, lane-linear per wave instruction);
 // STAGES-2 slices stay in flight across each barrier (counted vmcnt + raw s_barrier —
 // __syncthreads would drain them, cdna_hip_programming.md §5 "Pipelining across barriers").
-constexpr int vmcnt_imm(int n) { return (n & 15) | (7 << 4) | (15 << 8) | ((n >> 4) << 14); }
 
 template <int KB>
 __device__ __forceinline__ int swzk(int row, int chunk) {
@@ -258,7 +264,7 @@ __device__ __forceinline__ void big_epilogue(f32x4 (&acc)[MT][NT], uint16_t* dsm
         *(uint2*)(et + (i4 * 16 + fr) * EPI_LD + nl) = pk;
       }
     }
-    __builtin_amdgcn_s_waitcnt(0xC07F);
+    __builtin_amdgcn_s_waitcnt(LGKM0);
     __builtin_amdgcn_wave_barrier();
     // all LDS reads of the round first (unconditional; a read under the store's range test makes
     // hipcc wait for each one before the next), then the guarded stores
@@ -371,12 +377,12 @@ __global__ __launch_bounds__(512, 2 * OCC) void gemm_bf16_tn_big(const uint16_t*
   for (int kt = 0; kt < nk; ++kt) {
     const int after = min(STAGES - 2, nk - 1 - kt);  // slices issued after kt allowed in flight
     if (STAGES >= 4 && after >= 2) {
-      if (STAGES >= 5 && after >= 3) __builtin_amdgcn_s_waitcnt(vmcnt_imm(3 * PER_TILE));
-      else __builtin_amdgcn_s_waitcnt(vmcnt_imm(2 * PER_TILE));
+      if (STAGES >= 5 && after >= 3) __builtin_amdgcn_s_waitcnt(vmcnt_n(3 * PER_TILE));
+      else __builtin_amdgcn_s_waitcnt(vmcnt_n(2 * PER_TILE));
     } else if (STAGES >= 3 && after >= 1) {
-      __builtin_amdgcn_s_waitcnt(vmcnt_imm(PER_TILE));
+      __builtin_amdgcn_s_waitcnt(vmcnt_n(PER_TILE));
     } else {
-      __builtin_amdgcn_s_waitcnt(vmcnt_imm(0));
+      __builtin_amdgcn_s_waitcnt(vmcnt_n(0));
     }
     asm volatile("" ::: "memory");
     __builtin_amdgcn_s_barrier();
@@ -444,7 +450,7 @@ __global__ __launch_bounds__(512, 2 * OCC) void gemm_bf16_tn_big(const uint16_t*
         __builtin_amdgcn_sched_group_barrier(0x008, 2 * MT * NT, 0);
       }
     }
-    __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0): this slice's fragment reads returned
+    __builtin_amdgcn_s_waitcnt(LGKM0);  // lgkmcnt(0): this slice's fragment reads returned
   }
 
   big_epilogue<MT, NT, ACT, HAS_BIAS, HAS_RES>(acc, dsm, bias, R, Y, M, N, m0, n0, wm, wn, wave, lane);
@@ -485,8 +491,7 @@ __device__ __forceinline__ void ds_write_b64_untracked(const void* p, uint32_t l
 }
 __device__ __forceinline__ void ds_write_b128_untracked(const void* p, uint4 v) {
   const uint32_t a = (uint32_t)(uintptr_t)p;
-  typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
-  asm volatile("ds_write_b128 %0, %1" ::"v"(a), "v"(__builtin_bit_cast(u32x4_t, v)) : "memory");
+  asm volatile("ds_write_b128 %0, %1" ::"v"(a), "v"(__builtin_bit_cast(u32x4, v)) : "memory");
 }
 
 typedef int i32x8 __attribute__((ext_vector_type(8)));
@@ -507,8 +512,7 @@ __device__ __forceinline__ f32x4 mx_mfma(i32x8 a, i32x8 b, f32x4 c, uint32_t sa,
 // +4 %).  The permlane epilogue writes 64-B half lines and stays write-back (non-temporal: bf16 FFN1
 // -10 %), as do outputs the next kernel may find in the MALL.  profiles/r03_p8_nt_store_ab.txt.
 __device__ __forceinline__ void st16(void* p, uint4 v, bool nt) {
-  typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
-  if (nt) __builtin_nontemporal_store(__builtin_bit_cast(u32x4_t, v), (u32x4_t*)p);
+  if (nt) __builtin_nontemporal_store(__builtin_bit_cast(u32x4, v), (u32x4*)p);
   else *(uint4*)p = v;
 }
 
@@ -830,10 +834,9 @@ __global__ __launch_bounds__(512) void gemm_bf16_tn_p8(const uint16_t* __restric
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
   };
-  typedef _Float16 h8_t __attribute__((ext_vector_type(8)));
   auto mfma16 = [](bf16x8 a, bf16x8 b, f32x4 c) {
     if constexpr (KNN)
-      return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(h8_t, a), __builtin_bit_cast(h8_t, b), c, 0, 0, 0);
+      return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
     else
       return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
   };
@@ -854,7 +857,7 @@ __global__ __launch_bounds__(512) void gemm_bf16_tn_p8(const uint16_t* __restric
 #pragma unroll
     for (int j = 0; j < NT; ++j) gB(wb, 1, j, 1);
   }
-  __builtin_amdgcn_s_waitcnt(vmcnt_imm(4 + NT));
+  __builtin_amdgcn_s_waitcnt(vmcnt_n(4 + NT));
   barrier();
   if (wr == 1) barrier();  // stagger: m-group 1 runs one barrier behind
 
@@ -918,14 +921,13 @@ __global__ __launch_bounds__(512) void gemm_bf16_tn_p8(const uint16_t* __restric
             // native vector types on purpose: a HIP uint2 (struct) LDS read carries no TBAA, and hipcc
             // then waits vmcnt(0) for every in-flight LDS-DMA before it (drained the K-tile prefetch
             // at every K-tile: fp8 phases ran ~30 % longer than bf16's)
-            typedef uint32_t u32x2_t __attribute__((ext_vector_type(2)));
             typedef uint32_t u32x1_t __attribute__((ext_vector_type(1)));
             // lane offsets from a freshly computed lane id (opaque to hipcc): kept live across the
             // K loop they were spilled, and a spill reload is a vmcnt op that drains the prefetch
             int ll;
             asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(ll));
             const uint8_t* sb = (const uint8_t*)(dsm + soff(buf));
-            const u32x2_t sa2 = *(const u32x2_t*)(sb + wr * 512 + ll * 8);  // ((wr 4 + fq) 16 + fr) 8
+            const u32x2 sa2 = *(const u32x2*)(sb + wr * 512 + ll * 8);  // ((wr 4 + fq) 16 + fr) 8
             sca[0] = sa2[0];
             sca[1] = sa2[1];
             scb = (*(const u32x1_t*)(sb + 1024 + wc * 256 + ll * 4))[0];
@@ -961,13 +963,13 @@ __global__ __launch_bounds__(512) void gemm_bf16_tn_p8(const uint16_t* __restric
         };
         issue(2 * p);
         if (p == 3) {  // end of s6: O complete (younger: E pieces, + last tile's stores at it 0)
-          if (!loads) __builtin_amdgcn_s_waitcnt(vmcnt_imm(0));
-          else if (it == 0 && !first) __builtin_amdgcn_s_waitcnt(vmcnt_imm(5 + nstore + NRES));
-          else if (it == 0) __builtin_amdgcn_s_waitcnt(vmcnt_imm(5 + NRES));
-          else __builtin_amdgcn_s_waitcnt(vmcnt_imm(5));
+          if (!loads) __builtin_amdgcn_s_waitcnt(vmcnt_n(0));
+          else if (it == 0 && !first) __builtin_amdgcn_s_waitcnt(vmcnt_n(5 + nstore + NRES));
+          else if (it == 0) __builtin_amdgcn_s_waitcnt(vmcnt_n(5 + NRES));
+          else __builtin_amdgcn_s_waitcnt(vmcnt_n(5));
         } else if (p == 7) {  // end of s14: E complete (younger: 5 O pieces)
-          if (loads) __builtin_amdgcn_s_waitcnt(vmcnt_imm(5));
-          else __builtin_amdgcn_s_waitcnt(vmcnt_imm(0));
+          if (loads) __builtin_amdgcn_s_waitcnt(vmcnt_n(5));
+          else __builtin_amdgcn_s_waitcnt(vmcnt_n(0));
         }
         barrier();
         // ---- MFMA segment (s = 2p + 1)
@@ -1169,7 +1171,7 @@ __global__ __launch_bounds__(512) void gemm_bf16_tn_p8(const uint16_t* __restric
             ds_write_b128_untracked(grp + efr * RS + cc, __builtin_bit_cast(uint4, v));
           }
         }
-        __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0)
+        __builtin_amdgcn_s_waitcnt(LGKM0);  // lgkmcnt(0)
         barrier();
         // (2) rows 4 wc .. 4 wc + 3 of the round, row-major 16-B chunks (3 per lane)
         if constexpr (OSPL) {
@@ -1205,7 +1207,7 @@ __global__ __launch_bounds__(512) void gemm_bf16_tn_p8(const uint16_t* __restric
             else asm volatile("" ::"v"(ov[c]));
           }
         }
-        __builtin_amdgcn_s_waitcnt(0xC07F);  // the image is read before the next round overwrites it
+        __builtin_amdgcn_s_waitcnt(LGKM0);  // the image is read before the next round overwrites it
         barrier();
       }
     } else if constexpr (OF32) {
@@ -1349,7 +1351,7 @@ __global__ __launch_bounds__(512) void gemm_bf16_tn_p8(const uint16_t* __restric
           const int idx = c * 64 + le;
           ds_write_b128_untracked(et + (idx / (2 * NT)) * C::ELD + (idx % (2 * NT)) * 8, rr16[rd][c]);
         }
-        __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0)
+        __builtin_amdgcn_s_waitcnt(LGKM0);  // lgkmcnt(0)
         __builtin_amdgcn_wave_barrier();
       }
 #pragma unroll
@@ -1423,7 +1425,7 @@ __global__ __launch_bounds__(512) void gemm_bf16_tn_p8(const uint16_t* __restric
                 make_float2(st1, st2);
         }
       }
-      __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0)
+      __builtin_amdgcn_s_waitcnt(LGKM0);  // lgkmcnt(0)
       __builtin_amdgcn_wave_barrier();
       if constexpr (OUT8) {
         // lane: row le/4 of the round's 16 rows, columns 16 (le % 4) .. +15 of the wave's 64
@@ -1472,7 +1474,7 @@ __global__ __launch_bounds__(512) void gemm_bf16_tn_p8(const uint16_t* __restric
           else asm volatile("" ::"v"(ov[c]));
         }
       }
-      __builtin_amdgcn_s_waitcnt(0xC07F);
+      __builtin_amdgcn_s_waitcnt(LGKM0);
       __builtin_amdgcn_wave_barrier();
     }
     stamp(2);
@@ -1486,9 +1488,9 @@ __global__ __launch_bounds__(512) void gemm_bf16_tn_p8(const uint16_t* __restric
     first = false;
   }
   if (wr == 0) barrier();  // balance the stagger
-  __builtin_amdgcn_s_waitcnt(vmcnt_imm(0));
+  __builtin_amdgcn_s_waitcnt(vmcnt_n(0));
 #ifdef MMR_P8_STAMPS
-  __builtin_amdgcn_s_waitcnt(0xC07F);
+  __builtin_amdgcn_s_waitcnt(LGKM0);
   __syncthreads();
   if (blockIdx.x < 1024 && tid < 8 * 8 * 4) p8_stamps[blockIdx.x * 256 + tid] = lst[tid];
 #endif
@@ -1606,9 +1608,9 @@ __global__ __launch_bounds__(256) void gemm_bf16_tn_w4(const uint16_t* __restric
     for (int kt = 0; kt < nk; ++kt) {
       // glds of this slice were issued before: the previous tile's stores (kt = 0) or this tile's
       // epilogue operands (kt = 1) may stay in flight
-      if (kt == 0 && stores_out) __builtin_amdgcn_s_waitcnt(vmcnt_imm(NSTORE));
-      else if (kt == 1) __builtin_amdgcn_s_waitcnt(vmcnt_imm(NLOADS));
-      else __builtin_amdgcn_s_waitcnt(vmcnt_imm(0));
+      if (kt == 0 && stores_out) __builtin_amdgcn_s_waitcnt(vmcnt_n(NSTORE));
+      else if (kt == 1) __builtin_amdgcn_s_waitcnt(vmcnt_n(NLOADS));
+      else __builtin_amdgcn_s_waitcnt(vmcnt_n(0));
       asm volatile("" ::: "memory");
       __builtin_amdgcn_s_barrier();  // slice landed for every wave; the other stage is free
       asm volatile("" ::: "memory");
@@ -1684,7 +1686,7 @@ __global__ __launch_bounds__(256) void gemm_bf16_tn_w4(const uint16_t* __restric
         }
         *(uint2*)(et + fr * ELD + j * 16 + fq * 4) = make_uint2(mmr::pack2bf(v[0], v[1]), mmr::pack2bf(v[2], v[3]));
       }
-      __builtin_amdgcn_s_waitcnt(0xC07F);
+      __builtin_amdgcn_s_waitcnt(LGKM0);
       __builtin_amdgcn_wave_barrier();
 #pragma unroll
       for (int c = 0; c < CPL; ++c) {
@@ -1693,14 +1695,14 @@ __global__ __launch_bounds__(256) void gemm_bf16_tn_w4(const uint16_t* __restric
         const int n = n0 + wn * 16 * NT + (idx % CPR) * 8;
         *(bf16x8*)(Y + m * N + n) = *(const bf16x8*)(et + (idx / CPR) * ELD + (idx % CPR) * 8);
       }
-      __builtin_amdgcn_s_waitcnt(0xC07F);
+      __builtin_amdgcn_s_waitcnt(LGKM0);
       __builtin_amdgcn_wave_barrier();
     }
     if (!has_next) break;
     t = tnext;
     stores_out = true;
   }
-  __builtin_amdgcn_s_waitcnt(vmcnt_imm(0));  // no LDS-DMA may land after the workgroup retires
+  __builtin_amdgcn_s_waitcnt(vmcnt_n(0));  // no LDS-DMA may land after the workgroup retires
 }
 
 // ---------------------------------------------------------------- MX-fp8 quantizer
@@ -1760,17 +1762,6 @@ __global__ __launch_bounds__(256) void quantize_mxfp8(const uint16_t* __restrict
     }
     sc[off] = (uint8_t)(ex + 127);
   }
-}
-
-int cu_count() {
-  static int n = [] {
-    int dev = 0, v = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0)
-      v = 256;
-    return v;
-  }();
-  return n;
 }
 
 // Kernel variants: (w4, cfg) pairs the launcher understands.  w4: 0 no persistent kernel, 1 the
@@ -2098,7 +2089,7 @@ extern "C" mmr_status mmr_ln_row_coef(const float* stats, int64_t m, int32_t npa
   MMR_REQUIRE(m >= 0 && nparts > 0 && nparts % 2 == 0 && n > 0 && n % nparts == 0,
               "mmr_ln_row_coef: m=%lld nparts=%d n=%d (nparts even, equal parts of n / nparts columns)", (long long)m,
               nparts, n);
-  MMR_REQUIRE(((uintptr_t)stats & 15u) == 0 && ((uintptr_t)coef & 7u) == 0, "mmr_ln_row_coef: alignment");
+  MMR_REQUIRE(aligned16(stats) && ((uintptr_t)coef & 7u) == 0, "mmr_ln_row_coef: alignment");
   if (m == 0) return MMR_OK;
   ln_row_coef<<<dim3((unsigned)mmr::ceil_div(m * 8, 256)), dim3(256), 0, mmr::as_stream(stream)>>>(stats, m, nparts,
                                                                                               1.0f / (float)n, eps, coef);
@@ -2127,7 +2118,7 @@ extern "C" mmr_status mmr_x3_split_rows(const float* x, int64_t ldx, int64_t m, 
   const int64_t n8 = m * (kp / 8);
   const dim3 grid((unsigned)mmr::ceil_div(n8, 256));
   hipStream_t st = mmr::as_stream(stream);
-  if (((uintptr_t)x & 15) == 0 && ldx % 4 == 0 && k % 8 == 0)
+  if (aligned16(x) && ldx % 4 == 0 && k % 8 == 0)
     x3_split_rows<true><<<grid, 256, 0, st>>>(x, ldx, m, k, kp, xs);
   else
     x3_split_rows<false><<<grid, 256, 0, st>>>(x, ldx, m, k, kp, xs);

@@ -19,12 +19,13 @@
 
 namespace {
 
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+using mmr::bf16x8;
+using mmr::cu_count;
+using mmr::f32x16;
+using mmr::f32x4;
+using mmr::LGKM0;
+using mmr::vmcnt_n;
 typedef __attribute__((address_space(3))) void* lds_ptr_t;
-
-constexpr int vmcnt_n(int n) { return (n & 15) | (7 << 4) | (15 << 8) | ((n >> 4) << 14); }
 
 // physical 16-B unit of logical unit q in image row r: conflict-free ds_read_b128 for the 32x32x16
 // A-fragment pattern (rows lane & 31, unit 2ks + lane / 32), as swin_mlp.hip's unit_swz for 8n units
@@ -86,7 +87,7 @@ __global__ __launch_bounds__(64 * NW) void gemm_rw(const uint16_t* __restrict__ 
   bf16x8 xn[KS];
   if (tile < ntile) load_x(tile, xn);
   __builtin_amdgcn_s_waitcnt(vmcnt_n(0));  // the image's LDS-DMA landed
-  __builtin_amdgcn_s_waitcnt(0xC07F);      // lgkmcnt(0): the bias stores
+  __builtin_amdgcn_s_waitcnt(LGKM0);       // lgkmcnt(0): the bias stores
   asm volatile("" ::: "memory");
   __syncthreads();
   asm volatile("" ::: "memory");
@@ -142,16 +143,6 @@ __global__ __launch_bounds__(64 * NW) void gemm_rw(const uint16_t* __restrict__ 
       }
     }
   }
-}
-
-int cu_count() {
-  static int n = [] {
-    int dev = 0, v = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0)
-      v = 256;
-    return v;
-  }();
-  return n;
 }
 
 constexpr int RW_MAX_IMG = 150 * 1024;

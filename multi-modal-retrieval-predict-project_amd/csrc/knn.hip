@@ -50,15 +50,23 @@ hipError_t knn_scan_p8(const uint16_t* qh, const uint16_t* gh, int K, int tiles_
 
 namespace {
 
+using mmr::aligned16;
+using mmr::bf16x8;
 using mmr::ceil_div;
+using mmr::DeviceGuard;
+using mmr::f16x4;
+using mmr::f16x8;
+using mmr::f32x16;
+using mmr::f32x4;
+using mmr::LGKM0;
 using mmr::round_up;
+using mmr::u32x4;
+using mmr::vmcnt_n;
 
 constexpr int kSelThreads = 1024;
 constexpr int kCandCap = 2048;
 constexpr int kMaxK = 256;
 constexpr int kRowPad = 256;  // gallery rows padded to this (covers every scores tile width)
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 __device__ __forceinline__ uint32_t f2key(float f) {
   uint32_t u = __float_as_uint(f);
@@ -114,8 +122,7 @@ __host__ __device__ __forceinline__ int64_t tile32h_index(int64_t row, int k, in
 
 // 4 fp16 (one 8-B load) -> float4 (exact)
 __device__ __forceinline__ float4 h4_to_f4(uint2 u) {
-  typedef _Float16 h4 __attribute__((ext_vector_type(4)));
-  const h4 v = __builtin_bit_cast(h4, u);
+  const f16x4 v = __builtin_bit_cast(f16x4, u);
   return make_float4((float)v[0], (float)v[1], (float)v[2], (float)v[3]);
 }
 
@@ -177,7 +184,6 @@ __global__ __launch_bounds__(256) void knn_prep_queries(const float* __restrict_
   if ((tiled == 2 || tiled == 3) && Dp <= 1024) {
     // fp16 tile32h: lane owns the 8-half groups g = lane + 64j (j < 2) of the row — 16-B stores
     // (one (row, 8-half) run is contiguous in tile32h) instead of 2-B scatters; loads unconditional
-    typedef _Float16 h8 __attribute__((ext_vector_type(8)));
     const float* in = q + (row < nq ? row : 0) * (int64_t)d;
     float v[2][8];
     double ss = 0.0;
@@ -197,10 +203,10 @@ __global__ __launch_bounds__(256) void knn_prep_queries(const float* __restrict_
     for (int j = 0; j < 2; ++j) {
       const int k0 = 8 * (lane + 64 * j);
       if (k0 >= Dp) continue;
-      h8 o;
+      f16x8 o;
 #pragma unroll
       for (int e = 0; e < 8; ++e) o[e] = (_Float16)(v[j][e] * inv);
-      *(h8*)((_Float16*)qn + (tiled == 2 ? tile32h_index(row, k0, Dp) : row * (int64_t)Dp + k0)) = o;
+      *(f16x8*)((_Float16*)qn + (tiled == 2 ? tile32h_index(row, k0, Dp) : row * (int64_t)Dp + k0)) = o;
     }
     if (lane == 0) qnorm64[row] = row < nq ? nrm : 0.0;
     return;
@@ -314,8 +320,6 @@ __global__ __launch_bounds__(256) void knn_scores(const float* __restrict__ qn,
 }
 
 // ------------------------------------------------------------------ bf16x3 split scores GEMM
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) void* lds_ptr_t;
 
 __device__ __forceinline__ void split_bf16(float x, uint16_t& hi, uint16_t& lo) {
@@ -378,11 +382,10 @@ __global__ __launch_bounds__(256) void knn_tile_gallery_f16(const float* __restr
   const int64_t row = tile * 16 + r;
   const float ig = inv_g[row];
   const float* src = gal + row * Dp + c * 32 + 8 * h;
-  typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-  h8 v;
+  f16x8 v;
 #pragma unroll
   for (int e = 0; e < 8; ++e) v[e] = (_Float16)(src[e] * ig);
-  ((h8*)gh)[i] = v;
+  ((f16x8*)gh)[i] = v;
 }
 
 __device__ __forceinline__ int xswz(int row, int chunk) { return chunk ^ ((row >> 1) & 7); }
@@ -520,7 +523,6 @@ __global__ __launch_bounds__(64 * WQ) void knn_scan_f16_gmax(const uint16_t* __r
                                                         float* __restrict__ gmax, float* __restrict__ bmax,
                                                         int Dp, int64_t ldG, int64_t ldB, int64_t n,
                                                         const float* __restrict__ rs = nullptr) {
-  typedef _Float16 h8 __attribute__((ext_vector_type(8)));
   constexpr int L = KC / 32;  // 1-KB pieces per tile per chunk
   static_assert(!RAW || WQ == 1, "raw queries: one wave per block");
   const int lane = threadIdx.x & 63, wq = threadIdx.x >> 6;
@@ -548,12 +550,12 @@ __global__ __launch_bounds__(64 * WQ) void knn_scan_f16_gmax(const uint16_t* __r
     x[0] = *(const float4*)(qrow[t] + kk);
     x[1] = *(const float4*)(qrow[t] + kk + 4);
   };
-  auto qcvt = [&](int t, int k0, const float4 (&x)[2]) -> h8 {
+  auto qcvt = [&](int t, int k0, const float4 (&x)[2]) -> f16x8 {
     const bool ok = qok[t] && k0 < d;
-    h8 o;
+    f16x8 o;
     o[0] = (_Float16)x[0].x; o[1] = (_Float16)x[0].y; o[2] = (_Float16)x[0].z; o[3] = (_Float16)x[0].w;
     o[4] = (_Float16)x[1].x; o[5] = (_Float16)x[1].y; o[6] = (_Float16)x[1].z; o[7] = (_Float16)x[1].w;
-    return ok ? o : (h8){0, 0, 0, 0, 0, 0, 0, 0};
+    return ok ? o : (f16x8){0, 0, 0, 0, 0, 0, 0, 0};
   };
   f32x4 acc[QT][4];
 #pragma unroll
@@ -578,12 +580,12 @@ __global__ __launch_bounds__(64 * WQ) void knn_scan_f16_gmax(const uint16_t* __r
     for (int e = 0; e < L; ++e)
 #pragma unroll
       for (int t = 0; t < QT; ++t) {
-        h8 av;
+        f16x8 av;
         if constexpr (RAW) av = qcvt(t, kc + 32 * e + 8 * h, ra[t][e]);
-        else av = __builtin_bit_cast(h8, a[t][e]);
+        else av = __builtin_bit_cast(f16x8, a[t][e]);
 #pragma unroll
         for (int j = 0; j < 4; ++j)
-          acc[t][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(av, __builtin_bit_cast(h8, b[j][e]), acc[t][j], 0, 0, 0);
+          acc[t][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(av, __builtin_bit_cast(f16x8, b[j][e]), acc[t][j], 0, 0, 0);
       }
   };
   // both operands of the NEXT chunk are issued before this chunk's MFMAs (queries first: vmcnt
@@ -662,7 +664,6 @@ __global__ __launch_bounds__(64 * NWV) void knn_scan_f16_lq(const float* __restr
                                                           float* __restrict__ gmax, float* __restrict__ bmax,
                                                           int Dp, int64_t ldG, int64_t ldB, int64_t n, int64_t nblk,
                                                           double* __restrict__ qpre, const float* __restrict__ rs) {
-  typedef _Float16 h8 __attribute__((ext_vector_type(8)));
   constexpr int L = KC / 32;  // 1-KB pieces per tile per chunk
   extern __shared__ __attribute__((aligned(16))) uint16_t qs[];  // [QT][Dp/32][512] halfs
   const int tid = threadIdx.x, lane = tid & 63;
@@ -706,10 +707,10 @@ __global__ __launch_bounds__(64 * NWV) void knn_scan_f16_lq(const float* __restr
     const bool ok = row < nq && k0 < d;
     const float* src = qraw + (int64_t)(row < nq ? row : nq - 1) * d + (k0 < d ? k0 : d - 8);
     const float4 x0 = *(const float4*)src, x1 = *(const float4*)(src + 4);
-    h8 o;
+    f16x8 o;
     o[0] = (_Float16)x0.x; o[1] = (_Float16)x0.y; o[2] = (_Float16)x0.z; o[3] = (_Float16)x0.w;
     o[4] = (_Float16)x1.x; o[5] = (_Float16)x1.y; o[6] = (_Float16)x1.z; o[7] = (_Float16)x1.w;
-    *(h8*)(qs + tile32h_index(row, k0, Dp)) = ok ? o : (h8){0, 0, 0, 0, 0, 0, 0, 0};
+    *(f16x8*)(qs + tile32h_index(row, k0, Dp)) = ok ? o : (f16x8){0, 0, 0, 0, 0, 0, 0, 0};
   }
   __syncthreads();
   const int r = lane & 15, h = lane >> 4;
@@ -734,10 +735,10 @@ __global__ __launch_bounds__(64 * NWV) void knn_scan_f16_lq(const float* __restr
       for (int e = 0; e < L; ++e)
 #pragma unroll
         for (int t = 0; t < QT; ++t) {
-          const h8 av = *(const h8*)(qbase + ((int64_t)t * KP + kc / 32 + e) * 1024);
+          const f16x8 av = *(const f16x8*)(qbase + ((int64_t)t * KP + kc / 32 + e) * 1024);
 #pragma unroll
           for (int j = 0; j < 4; ++j)
-            acc[t][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(av, __builtin_bit_cast(h8, b[j][e]), acc[t][j], 0, 0, 0);
+            acc[t][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(av, __builtin_bit_cast(f16x8, b[j][e]), acc[t][j], 0, 0, 0);
         }
     };
     // the next chunk's gallery pieces are issued before this chunk's MFMAs; the last chunk is peeled
@@ -827,7 +828,7 @@ struct F16TileCfg {
 __device__ __forceinline__ void wait_vm(int n) {
   // s_waitcnt vmcnt(n) for a wave-uniform runtime n in [0, 63] (rare path: the end of the stream)
   switch (n) {
-#define MMR_VM(N) case N: __builtin_amdgcn_s_waitcnt(((N) & 15) | (7 << 4) | (15 << 8) | (((N) >> 4) << 14)); break;
+#define MMR_VM(N) case N: __builtin_amdgcn_s_waitcnt(vmcnt_n(N)); break;
     MMR_VM(0) MMR_VM(1) MMR_VM(2) MMR_VM(3) MMR_VM(4) MMR_VM(5) MMR_VM(6) MMR_VM(7) MMR_VM(8) MMR_VM(9)
     MMR_VM(10) MMR_VM(11) MMR_VM(12) MMR_VM(13) MMR_VM(14) MMR_VM(15) MMR_VM(16) MMR_VM(17) MMR_VM(18)
     MMR_VM(19) MMR_VM(20) MMR_VM(21) MMR_VM(22) MMR_VM(23) MMR_VM(24) MMR_VM(25) MMR_VM(26) MMR_VM(27)
@@ -867,7 +868,6 @@ __global__ __launch_bounds__(64 * WQ * WR) void knn_scan_f16_tile(const uint16_t
                                                                   int Dp, int64_t ldG, int64_t ldB, int64_t n,
                                                                   int64_t n_rt, const float* __restrict__ rs) {
   using C = F16TileCfg<WQ, MQ, WR, MR, PF>;
-  typedef _Float16 h8 __attribute__((ext_vector_type(8)));
   extern __shared__ __attribute__((aligned(16))) uint16_t dsm[];  // [STAGES][P][512] halfs
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -917,7 +917,7 @@ __global__ __launch_bounds__(64 * WQ * WR) void knn_scan_f16_tile(const uint16_t
   };
   const uint32_t lane_b = lane * 16;
   auto frag = [&](int stage, int piece) {
-    return *(const h8*)((const char*)dsm + stage * C::SLICE_B + piece * 1024 + lane_b);
+    return *(const f16x8*)((const char*)dsm + stage * C::SLICE_B + piece * 1024 + lane_b);
   };
   // wait until this wave's pieces of the slice `ahead_of` slices before the cursor end landed
   int waited = 0;  // slices whose pieces this wave has waited for
@@ -936,7 +936,7 @@ __global__ __launch_bounds__(64 * WQ * WR) void knn_scan_f16_tile(const uint16_t
     __builtin_amdgcn_s_barrier();  // every wave's pieces landed; every wave is past the previous step
     asm volatile("" ::: "memory");
   };
-  h8 fa[MR], fb0[MQ], fb1[MQ];
+  f16x8 fa[MR], fb0[MQ], fb1[MQ];
   f32x4 acc[MQ][MR];
   // prologue: STAGES-1 slices in flight
 #pragma unroll
@@ -951,7 +951,7 @@ __global__ __launch_bounds__(64 * WQ * WR) void knn_scan_f16_tile(const uint16_t
   }
   // one step: slice (tile, kp) in ring slot `stage`; with PF its fragments are in (fa, fb) and the
   // next slice's are read into (fa, nb)
-  auto step = [&](int tile, int kp, int64_t rt0, bool active, h8 (&fb)[MQ], h8 (&nb)[MQ]) {
+  auto step = [&](int tile, int kp, int64_t rt0, bool active, f16x8 (&fb)[MQ], f16x8 (&nb)[MQ]) {
     const bool more = tile + 1 < ntiles || kp + 1 < KP;
     if (PF) {
       if (more) wait_slice();  // slice s+1 (for the fragment prefetch)
@@ -978,7 +978,7 @@ __global__ __launch_bounds__(64 * WQ * WR) void knn_scan_f16_tile(const uint16_t
         }
       }
     }
-    __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0): this step's fragment reads returned
+    __builtin_amdgcn_s_waitcnt(LGKM0);  // lgkmcnt(0): this step's fragment reads returned
     stage = nstage;
     if (kp == KP - 1 && active) {
       // epilogue: lane (query tile t, query qc, rows 16 rt + 4h .. +3) -> unit max; 4x4 lane transpose
@@ -1384,7 +1384,6 @@ __device__ uint32_t block_kth_lower_top4(uint32_t key, int kth, uint32_t* vals, 
   __syncthreads();
   // every wave ranks the NV candidates itself from LDS broadcast reads (one wave ranking them by lane
   // swaps, then two more barriers to broadcast its pick, cost ~0.5 us of the phase)
-  typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
   const uint32_t mine = lane < NV ? vals[lane] : 0u;
   int rank = 0;  // values ahead of mine (larger, or equal at a lower position)
 #pragma unroll
@@ -2228,17 +2227,6 @@ constexpr int64_t kSkinnyMaxQ = 32;
 // query tiles per p8 pass with 4-row units (2 / 4 measured: 4, profiles/r03_s4_knn_pair_ab.txt)
 constexpr int kP8PairTiles = 4;
 
-struct DeviceGuard {
-  int prev = -1;
-  explicit DeviceGuard(int dev) {
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    if (prev != dev) (void)hipSetDevice(dev);
-  }
-  ~DeviceGuard() {
-    if (prev >= 0) (void)hipSetDevice(prev);
-  }
-};
-
 template <int WQ, int MQ, int WR, int MR, bool PF>
 void launch_f16_tile(hipStream_t st, const mmr_index* ix, const uint16_t* qh, float* gm, float* bm, int64_t ldG,
                      int64_t ldB, int64_t n_rt) {
@@ -2587,7 +2575,7 @@ mmr_status mmr_index_search(mmr_index* ix, const float* q, int64_t nq, int32_t k
           continue;
         }
         const dim3 grid((unsigned)(ix->Np / 64));
-        if (qt <= 2 && ix->d % 8 == 0 && ((uintptr_t)qp & 15) == 0) {
+        if (qt <= 2 && ix->d % 8 == 0 && aligned16(qp)) {
           // <= 32 queries: the scan reads the caller's f32 rows itself (no prep launch), per-query margin
           const int64_t nqp = pq;
           const bool lq = ix->Dp <= 1024;

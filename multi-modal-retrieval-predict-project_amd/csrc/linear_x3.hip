@@ -18,24 +18,12 @@
 
 namespace {
 
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+using mmr::aligned16;
+using mmr::bf16x8;
+using mmr::f32x4;
+using mmr::split8;
 
 constexpr int X3_CH = 3;  // k-steps (32 k each) per load chunk
-
-__device__ __forceinline__ void split8(const float4& p, const float4& q, bf16x8& hi, bf16x8& lo) {
-  const float v[8] = {p.x, p.y, p.z, p.w, q.x, q.y, q.z, q.w};
-  uint32_t h[4], l[4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    h[j] = mmr::pack2bf(v[2 * j], v[2 * j + 1]);
-    const float r0 = v[2 * j] - __uint_as_float(h[j] << 16);
-    const float r1 = v[2 * j + 1] - __uint_as_float(h[j] & 0xFFFF0000u);
-    l[j] = mmr::pack2bf(r0, r1);
-  }
-  hi = __builtin_bit_cast(bf16x8, make_uint4(h[0], h[1], h[2], h[3]));
-  lo = __builtin_bit_cast(bf16x8, make_uint4(l[0], l[1], l[2], l[3]));
-}
 
 template <int ACT, bool BIAS, bool RES, int NW>
 __global__ __launch_bounds__(64 * NW) void linear_x3(const float* __restrict__ X, int64_t ldx,
@@ -139,7 +127,7 @@ extern "C" mmr_status mmr_linear_x3(const float* x, int64_t ldx, int64_t bsx, co
               "mmr_linear_x3: cin=%d must be a multiple of 128, cout=%d of 32", cin, cout);
   MMR_REQUIRE(ldx >= cin && ldx % 4 == 0 && bsx % 4 == 0 && bsw % 8 == 0 && ldy >= cout && (!residual || ldr >= cout),
               "mmr_linear_x3: bad strides");
-  MMR_REQUIRE(((uintptr_t)x & 15u) == 0 && ((uintptr_t)w_hi & 15u) == 0 && ((uintptr_t)w_lo & 15u) == 0,
+  MMR_REQUIRE(aligned16(x) && aligned16(w_hi) && aligned16(w_lo),
               "mmr_linear_x3: x / w must be 16-B aligned");
   MMR_REQUIRE(act == 0 || act == 1, "mmr_linear_x3: act=%d", act);
   if (b == 0) return MMR_OK;

@@ -27,25 +27,16 @@
 
 namespace {
 
+using mmr::aligned16;
+using mmr::DeviceGuard;
+using mmr::f16x8;
+using mmr::f32x4;
 typedef double f64x4 __attribute__((ext_vector_type(4)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 
 constexpr int RE_QT = 32;            // queries per workgroup
 constexpr int RE_ROWS = 256;         // gallery rows per workgroup (= kRowPad of knn.hip: Np % 256 == 0)
 constexpr int64_t RE_CHUNK = 1024;   // queries per pass (bounds the workspace)
 constexpr int64_t RE_NONE = INT64_MAX;
-
-struct DeviceGuard {
-  int prev = -1;
-  explicit DeviceGuard(int dev) {
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    if (prev != dev) (void)hipSetDevice(dev);
-  }
-  ~DeviceGuard() {
-    if (prev >= 0) (void)hipSetDevice(prev);
-  }
-};
 
 // (score desc, index asc); "none" is (-inf, RE_NONE)
 __device__ __forceinline__ bool re_better(double s, int64_t i, double s2, int64_t i2) {
@@ -377,7 +368,7 @@ mmr_status mmr_index_best_relevant(const mmr_index* ix, const float* q, int64_t 
   if (nq == 0) return MMR_OK;
   MMR_REQUIRE(q && q_labels && out_idx, "mmr_index_best_relevant: NULL q / q_labels / out_idx");
   MMR_REQUIRE(ix->n == 0 || g_labels, "mmr_index_best_relevant: g_labels is NULL");
-  MMR_REQUIRE(work && ((uintptr_t)work & 15u) == 0, "mmr_index_best_relevant: work is NULL or not 16-B aligned");
+  MMR_REQUIRE(work && aligned16(work), "mmr_index_best_relevant: work is NULL or not 16-B aligned");
   return re_run(ix, q, nq, 0, q_labels, g_labels, exclude, nullptr, nullptr, out_idx, out_score, out_nrel, work, stream);
 }
 
@@ -389,7 +380,7 @@ mmr_status mmr_index_count_ahead(const mmr_index* ix, const float* q, int64_t nq
   MMR_REQUIRE(nq >= 0, "mmr_index_count_ahead: nq < 0");
   if (nq == 0) return MMR_OK;
   MMR_REQUIRE(q && ref_idx && ref_score && out_ahead, "mmr_index_count_ahead: NULL q / ref_idx / ref_score / out_ahead");
-  MMR_REQUIRE(work && ((uintptr_t)work & 15u) == 0, "mmr_index_count_ahead: work is NULL or not 16-B aligned");
+  MMR_REQUIRE(work && aligned16(work), "mmr_index_count_ahead: work is NULL or not 16-B aligned");
   return re_run(ix, q, nq, 1, nullptr, nullptr, exclude, ref_idx, ref_score, nullptr, nullptr, out_ahead, work, stream);
 }
 

@@ -25,12 +25,15 @@
 
 namespace {
 
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
+using mmr::bf16x8;
+using mmr::cu_count;
+using mmr::f32x16;
+using mmr::f32x4;
+using mmr::half_max;
+using mmr::half_sum;
+using mmr::LGKM0;
+using mmr::vmcnt_n;
 typedef __attribute__((address_space(3))) void* lds_ptr_t;
-
-constexpr int vmcnt_n(int n) { return (n & 15) | (7 << 4) | (15 << 8) | ((n >> 4) << 14); }
 
 constexpr int AC = 96, AH = 3, ADH = 32, AWS = 7, ATOK = 49;
 constexpr int QKV_E = 3 * AC * AC;            // bf16 elements of the QKV image
@@ -98,15 +101,6 @@ __device__ __forceinline__ f2 pk(float a, float b) { return (f2){a, b}; }
 // two bf16 of a packed dword -> f32 pair (2 VALU: shift + and)
 __device__ __forceinline__ f2 bf2x(uint32_t u) { return (f2){__uint_as_float(u << 16), __uint_as_float(u & 0xffff0000u)}; }
 __device__ __forceinline__ f2 fma2(f2 a, f2 b, f2 c) { return __builtin_elementwise_fma(a, b, c); }
-// reductions across the two lane halves (lane l and l ^ 32): v_permlane32_swap, no LDS round trip
-__device__ __forceinline__ float half_sum(float v) {
-  const auto p = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-  return __uint_as_float(p[0]) + __uint_as_float(p[1]);
-}
-__device__ __forceinline__ float half_max(float v) {
-  const auto p = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-  return fmaxf(__uint_as_float(p[0]), __uint_as_float(p[1]));
-}
 
 // VALU budget (the kernel is VALU-issue-bound: one wave64 VALU op occupies the SIMD 4 cycles, a
 // 32x32x16 MFMA 32): all index math is 32-bit with per-lane token coordinates hoisted out of the
@@ -186,7 +180,7 @@ __global__ __launch_bounds__(NWV * 64) __attribute__((amdgpu_waves_per_eu(2, 2))
   __syncthreads();  // gather table
   if (win < total) gather(win_of(win), lane);
   __builtin_amdgcn_s_waitcnt(vmcnt_n(0));
-  __builtin_amdgcn_s_waitcnt(0xC07F);
+  __builtin_amdgcn_s_waitcnt(LGKM0);
   asm volatile("" ::: "memory");
   __builtin_amdgcn_s_barrier();  // weights visible to every wave; no barrier after this point
   asm volatile("" ::: "memory");
@@ -405,7 +399,7 @@ __global__ __launch_bounds__(NWV * 64) __attribute__((amdgpu_waves_per_eu(2, 2))
 #pragma unroll
         for (int hf = 0; hf < 2; ++hf) xv[t2][u][hf] = *(const uint4*)(xr + 32 * u + 16 * hf + 8 * h);
     }
-    __builtin_amdgcn_s_waitcnt(0xC07F);  // LN's reads of the buffer (long done) before the DMA
+    __builtin_amdgcn_s_waitcnt(LGKM0);  // LN's reads of the buffer (long done) before the DMA
     asm volatile("" ::: "memory");
     if (win + stride < total) gather(win_of(win + stride), lnv);
     // the proj's lane values from a fresh opaque lane id: an address kept from the LN phase was
@@ -461,17 +455,6 @@ __global__ __launch_bounds__(NWV * 64) __attribute__((amdgpu_waves_per_eu(2, 2))
     }
   }
   __builtin_amdgcn_s_waitcnt(vmcnt_n(0));  // no LDS-DMA may land after the workgroup retires
-}
-
-int cu_count() {
-  static int n = [] {
-    int dev = 0, v = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0)
-      v = 256;
-    return v;
-  }();
-  return n;
 }
 
 }  // namespace

@@ -22,15 +22,16 @@
 
 namespace {
 
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+using mmr::bf16x8;
+using mmr::cu_count;
+using mmr::f32x16;
+using mmr::f32x4;
+using mmr::LGKM0;
+using mmr::vmcnt_n;
 // NOTE: LDS reads below use native vector types on purpose.  A HIP float4 (struct) load carries no
 // TBAA info, and hipcc then makes every such ds_read wait vmcnt(0) for all in-flight
 // global_load_lds — draining the weight ring each time.
 typedef __attribute__((address_space(3))) void* lds_ptr_t;
-
-constexpr int vmcnt_n(int n) { return (n & 15) | (7 << 4) | (15 << 8) | ((n >> 4) << 14); }
 
 // Geometry.  NW waves per workgroup, 32 tokens per wave (the N side of
 // v_mfma_f32_32x32x16_bf16).  Hidden units are walked in HC-wide chunks; a chunk is
@@ -143,7 +144,7 @@ __global__ __launch_bounds__(64 * NW) void swin_mlp(const uint16_t* __restrict__
   if constexpr (R == 3) stage(1);
   // x and the parameters were issued before the chunk(s): wait for them only
   __builtin_amdgcn_s_waitcnt(vmcnt_n((R - 1) * G::PW));
-  __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0): parameter stores landed
+  __builtin_amdgcn_s_waitcnt(LGKM0);  // lgkmcnt(0): parameter stores landed
   asm volatile("" ::: "memory");
   __builtin_amdgcn_s_barrier();
   asm volatile("" ::: "memory");
@@ -305,7 +306,7 @@ __global__ __launch_bounds__(64 * NW) void swin_mlp_sp(const uint16_t* __restric
   bf16x8 xn[G::KS1];
   load_x(tile, xn);
   __builtin_amdgcn_s_waitcnt(vmcnt_n(0));
-  __builtin_amdgcn_s_waitcnt(0xC07F);
+  __builtin_amdgcn_s_waitcnt(LGKM0);
   asm volatile("" ::: "memory");
   __builtin_amdgcn_s_barrier();
   asm volatile("" ::: "memory");
@@ -446,16 +447,6 @@ __global__ __launch_bounds__(64 * NW) void swin_mlp_sp(const uint16_t* __restric
         }
     }
   }
-}
-
-int cu_count() {
-  static int n = [] {
-    int dev = 0, v = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0)
-      v = 256;
-    return v;
-  }();
-  return n;
 }
 
 template <int C, int NW, bool FAST>

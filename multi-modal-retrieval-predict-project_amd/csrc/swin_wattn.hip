@@ -38,13 +38,13 @@
 
 namespace {
 
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
-typedef short bf16x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+using mmr::bf16x4;
+using mmr::bf16x8;
+using mmr::f32x16;
+using mmr::LGKM0;
+using mmr::u32x2;
+using mmr::vmcnt_n;
 typedef __attribute__((address_space(3))) void* lds_ptr_t;
-
-constexpr int vmcnt_n(int n) { return (n & 15) | (7 << 4) | (15 << 8) | ((n >> 4) << 14); }
 
 constexpr int SWS = 7, STOK = 49;
 constexpr int NW = mmr::SWA_STREAM_WAVES;
@@ -272,7 +272,7 @@ __global__ __launch_bounds__(NW * 64) void swin_wattn_stream(const uint16_t* __r
     Frags fr[2];
     read_frags(im, 0, fr[0]);
     read_frags(im, 1, fr[1]);
-    __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0): also `other` read out before the DMA writes it
+    __builtin_amdgcn_s_waitcnt(LGKM0);  // lgkmcnt(0): also `other` read out before the DMA writes it
     asm volatile("" ::: "memory");
     const bool more = i + 1 < i1;
     const Unit nd = more ? unit_of(i + 1) : ud;
@@ -287,17 +287,6 @@ __global__ __launch_bounds__(NW * 64) void swin_wattn_stream(const uint16_t* __r
   }
   store_out(pd, img0 + (buf ^ 1) * IMG_B);
   __builtin_amdgcn_s_waitcnt(vmcnt_n(0));
-}
-
-int cu_count() {
-  static int n = [] {
-    int dev = 0, v = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0)
-      v = 256;
-    return v;
-  }();
-  return n;
 }
 
 }  // namespace

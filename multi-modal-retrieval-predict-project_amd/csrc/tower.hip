@@ -13,13 +13,14 @@
 
 namespace {
 
+using mmr::aligned16;
+using mmr::bf16x4;
+using mmr::bf16x8;
 using mmr::bf2f;
 using mmr::f2bf;
-
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
-typedef short bf16x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+using mmr::f32x16;
+using mmr::f32x4;
+using mmr::LGKM0;
 
 __device__ __forceinline__ void load8(const uint16_t* p, float* v) {
   bf16x8 x = *(const bf16x8*)p;
@@ -377,7 +378,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void s
     __builtin_amdgcn_sched_barrier(0);  // every load above in flight before the first use
 #pragma unroll
     for (int it = 0; it < 4; ++it) *(bf16x8*)(vs + (16 * it + (lane >> 2)) * VROW + (lane & 3) * 8) = vr[it];
-    __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0): this wave's V rows are in LDS
+    __builtin_amdgcn_s_waitcnt(LGKM0);  // lgkmcnt(0): this wave's V rows are in LDS
     __builtin_amdgcn_wave_barrier();
     asm volatile("" ::: "memory");
 
@@ -1107,7 +1108,7 @@ mmr_status mmr_patch_im2col(const float* image, uint16_t* cols, int32_t b, int32
   const int64_t ntok = (int64_t)b * (hw / patch) * (hw / patch);
   if (ntok == 0) return MMR_OK;
   if (patch == 4 && cin == 3 && hw % 4 == 0 && (int64_t)b * 3 * hw * hw < (int64_t(1) << 31) &&
-      ((uintptr_t)image & 15u) == 0)
+      aligned16(image))
     patch_im2col_p4c3<<<dim3((unsigned)mmr::ceil_div(ntok * 8, 256)), 256, 0, mmr::as_stream(stream)>>>(
         image, cols, (uint32_t)ntok, (uint32_t)hw);
   else
@@ -1221,7 +1222,7 @@ mmr_status mmr_linear_f32(const float* x, int64_t ldx, const float* w, const flo
   MMR_REQUIRE(cin % 16 == 0 && cout % 32 == 0, "mmr_linear_f32: cin=%d must be a multiple of 16, cout=%d of 32", cin, cout);
   MMR_REQUIRE(ldx >= cin && ldx % 4 == 0 && ldy >= cout && (!residual || ldr >= cout),
               "mmr_linear_f32: bad row strides");
-  MMR_REQUIRE(((uintptr_t)x & 15u) == 0 && ((uintptr_t)w & 15u) == 0, "mmr_linear_f32: x / w must be 16-B aligned");
+  MMR_REQUIRE(aligned16(x) && aligned16(w), "mmr_linear_f32: x / w must be 16-B aligned");
   MMR_REQUIRE(act == 0 || act == 1, "mmr_linear_f32: act=%d", act);
   if (b == 0) return MMR_OK;
   launch_linear_f32(x, w, bias, y, b, cin, cout, act, ldx, ldy, residual, ldr, mmr::as_stream(stream));
@@ -1239,7 +1240,7 @@ mmr_status mmr_linear_f32_batched(const float* x, int64_t ldx, int64_t bsx, cons
               cin, cout);
   MMR_REQUIRE(ldx >= cin && ldx % 4 == 0 && ldy >= cout && (!residual || ldr >= cout) && bsx % 4 == 0 && bsw % 4 == 0,
               "mmr_linear_f32_batched: bad strides");
-  MMR_REQUIRE(((uintptr_t)x & 15u) == 0 && ((uintptr_t)w & 15u) == 0, "mmr_linear_f32_batched: x / w must be 16-B aligned");
+  MMR_REQUIRE(aligned16(x) && aligned16(w), "mmr_linear_f32_batched: x / w must be 16-B aligned");
   MMR_REQUIRE(act == 0 || act == 1, "mmr_linear_f32_batched: act=%d", act);
   if (b == 0) return MMR_OK;
   launch_linear_f32(x, w, bias, y, b, cin, cout, act, ldx, ldy, residual, ldr, mmr::as_stream(stream), nbatch, bsx,

@@ -30,13 +30,19 @@
 
 namespace {
 
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
-typedef short bf16x4 __attribute__((ext_vector_type(4)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
+using mmr::aligned16;
+using mmr::bf16x4;
+using mmr::bf16x8;
+using mmr::f32x16;
+using mmr::f32x4;
+using mmr::LGKM0;
+using mmr::mfma3;
 typedef __attribute__((address_space(3))) bf16x4 lds_bf16x4;
 
-// f32 x4 -> (hi, lo) bf16 x4 each, packed as two dwords
+// f32 x4 -> (hi, lo) bf16 x4 each, packed as two dwords: mmr::split2's arithmetic with both hi words formed first.
+// Kept apart from it: built on mmr::split2 the kernels hold the same instructions in another order, and x3_mha at
+// Swin stage 3 (hw 14, C = 384) ran 96.7 against 93.4 us, same-build spread 1.5 us (tools/x3_attn_bench.py through
+// tools/ab_lib_swap.sh on one MI355X; the other shapes within their spread)
 __device__ __forceinline__ void split4(const float4 v, uint2& hi, uint2& lo) {
   const uint32_t h0 = mmr::pack2bf(v.x, v.y), h1 = mmr::pack2bf(v.z, v.w);
   const float r0 = v.x - __uint_as_float(h0 << 16), r1 = v.y - __uint_as_float(h0 & 0xFFFF0000u);
@@ -52,16 +58,6 @@ __device__ __forceinline__ void split8(const float4 a, const float4 b, bf16x8& h
   hi = __builtin_bit_cast(bf16x8, make_uint4(h0.x, h0.y, h1.x, h1.y));
   lo = __builtin_bit_cast(bf16x8, make_uint4(l0.x, l0.y, l1.x, l1.y));
 }
-
-__device__ __forceinline__ f32x4 mfma3(const bf16x8 ah, const bf16x8 al, const bf16x8 bh, const bf16x8 bl, f32x4 acc) {
-  acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bh, acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bl, acc, 0, 0, 0);
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(al, bh, acc, 0, 0, 0);
-}
-
-// GELU (erf form, as torch) with erf by Abramowitz-Stegun 7.1.26 (|err| <= 1.5e-7, mmr::gelu_erf): 100x below
-// the bf16x3 products' 2^-17, branch-free (ocml erff made the GEMM epilogues VALU-heavy)
-__device__ __forceinline__ float gelu_exact(float x) { return mmr::gelu_erf(x); }
 
 // ------------------------------------------------------------------ GEMM
 constexpr int GX_BM = 128, GX_BN = 128, GX_BK = 32, GX_LD = 40;  // LDS row stride 80 B: conflict-free 16-B reads
@@ -152,7 +148,7 @@ __global__ __launch_bounds__(256, 2) void x3_gemm(const float* __restrict__ X, i
         if (row >= M) continue;
         float v = acc[m][n][i];
         if (BIAS) v += bv;
-        if (ACT == 1) v = gelu_exact(v);
+        if (ACT == 1) v = mmr::gelu_erf(v);  // erf form, as torch (ocml erff made the epilogues VALU-heavy)
         if (RES) v += R[(int64_t)row * ldr + col];
         Y[(int64_t)row * ldy + col] = v;
       }
@@ -470,7 +466,7 @@ __global__ __launch_bounds__(256, DT <= 2 ? 3 : 2) void x3_mha(const AttnArgs a,
         for (int g4 = 0; g4 < 4; ++g4)
           *(float4*)(st + r * OROW + dt * 32 + 8 * g4 + 4 * hf) =
               make_float4(o[dt][4 * g4] * inv, o[dt][4 * g4 + 1] * inv, o[dt][4 * g4 + 2] * inv, o[dt][4 * g4 + 3] * inv);
-      __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0): this wave's LDS writes landed
+      __builtin_amdgcn_s_waitcnt(LGKM0);  // lgkmcnt(0): this wave's LDS writes landed
       __builtin_amdgcn_wave_barrier();
       // lane -> (row lr + rpi j, 4-column chunk lc): the divisions once per lane, not per chunk
       const int nc4 = dh / 4, rpi = 64 / nc4, lr = lane / nc4, lc = lane - lr * nc4;
@@ -812,13 +808,11 @@ __global__ __launch_bounds__(256) void x3_gather_rows(const float* __restrict__ 
   y[i] = x[(i / c) * ldx + (i % c)];
 }
 
-bool al16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
-
 mmr_status launch_attention(const char* who, AttnArgs a, int64_t nbh, bool swin, void* stream) {
   MMR_REQUIRE(a.q && a.k && a.v && (a.out || a.mean_out || a.xs), "%s: NULL pointer", who);
   MMR_REQUIRE(a.lq > 0 && a.lk > 0 && a.heads > 0 && a.dh > 0 && a.dh % 8 == 0 && a.dh <= 128,
               "%s: bad shape lq=%d lk=%d heads=%d dh=%d (dh %% 8 == 0, <= 128)", who, a.lq, a.lk, a.heads, a.dh);
-  MMR_REQUIRE(a.ldq % 4 == 0 && a.ldk % 4 == 0 && a.ldv % 4 == 0 && al16(a.q) && al16(a.k) && al16(a.v) &&
+  MMR_REQUIRE(a.ldq % 4 == 0 && a.ldk % 4 == 0 && a.ldv % 4 == 0 && aligned16(a.q) && aligned16(a.k) && aligned16(a.v) &&
                   (((int64_t)a.heads * a.dh) <= a.ldq),
               "%s: rows must be 16-B aligned with strides >= heads*dh", who);
   if (nbh == 0) return MMR_OK;
@@ -885,7 +879,7 @@ mmr_status mmr_x3_linear(const float* x, int64_t ldx, const uint16_t* w_hi, cons
   MMR_REQUIRE(x && w_hi && w_lo && y && m >= 0 && n > 0 && k > 0, "mmr_x3_linear: bad arguments");
   MMR_REQUIRE(k % 32 == 0 && ldx >= k && ldx % 4 == 0 && ldy >= n && (!residual || ldr >= n),
               "mmr_x3_linear: k=%d must be a multiple of 32 (ldx=%lld ldy=%lld)", k, (long long)ldx, (long long)ldy);
-  MMR_REQUIRE(al16(x) && al16(w_hi) && al16(w_lo), "mmr_x3_linear: x / w must be 16-B aligned");
+  MMR_REQUIRE(aligned16(x) && aligned16(w_hi) && aligned16(w_lo), "mmr_x3_linear: x / w must be 16-B aligned");
   MMR_REQUIRE(act == 0 || act == 1, "mmr_x3_linear: act=%d", act);
   MMR_REQUIRE(m < (int64_t(1) << 31), "mmr_x3_linear: m=%lld too large", (long long)m);
   if (m == 0) return MMR_OK;
@@ -968,7 +962,7 @@ mmr_status mmr_x3_patch_im2col(const float* image, float* cols, int32_t b, int32
               "mmr_x3_patch_im2col: bad arguments");
   const int64_t ntok = (int64_t)b * (hw / patch) * (hw / patch);
   if (ntok == 0) return MMR_OK;
-  if (patch == 4 && hw % 4 == 0 && kp % 4 == 0 && al16(image) && al16(cols))
+  if (patch == 4 && hw % 4 == 0 && kp % 4 == 0 && aligned16(image) && aligned16(cols))
     x3_im2col_p4<<<dim3((unsigned)mmr::ceil_div(ntok * (kp / 4), 256)), 256, 0, mmr::as_stream(stream)>>>(
         image, cols, ntok, cin, hw, kp);
   else
@@ -985,7 +979,7 @@ mmr_status mmr_x3_patch_merge_ln(const float* x, const float* gamma, const float
               "mmr_x3_patch_merge_ln: bad arguments (4c <= 4096)");
   const int64_t nout = (int64_t)b * (hw / 2) * (hw / 2);
   if (nout == 0) return MMR_OK;
-  if (c % 4 == 0 && al16(x) && al16(gamma) && al16(beta) && al16(y))
+  if (c % 4 == 0 && aligned16(x) && aligned16(gamma) && aligned16(beta) && aligned16(y))
     return launch_patch_merge_v(x, gamma, beta, y, nullptr, 0, nout, hw, c, eps, mmr::as_stream(stream));
   x3_patch_merge_ln<<<dim3((unsigned)mmr::ceil_div(nout, 4)), 256, 0, mmr::as_stream(stream)>>>(x, gamma, beta, y, nout,
                                                                                                hw, c, eps);
@@ -998,7 +992,7 @@ mmr_status mmr_x3_patch_merge_ln_xs(const float* x, const float* gamma, const fl
   mmr::clear_error();
   const int kp = mmr_x3_p8_kpad(4 * c);
   MMR_REQUIRE(x && gamma && beta && xs && b >= 0 && hw % 2 == 0 && c > 0 && c % 4 == 0 && 4 * c <= 4096 && kp > 0 &&
-                  al16(x) && al16(gamma) && al16(beta) && al16(xs),
+                  aligned16(x) && aligned16(gamma) && aligned16(beta) && aligned16(xs),
               "mmr_x3_patch_merge_ln_xs: bad arguments (c %% 4 == 0, 4c <= 4096, 16-B aligned)");
   const int64_t nout = (int64_t)b * (hw / 2) * (hw / 2);
   if (nout == 0) return MMR_OK;
@@ -1024,7 +1018,7 @@ mmr_status mmr_x3_add_pos(const float* x, const float* pos, float* y, int64_t ro
   mmr::clear_error();
   MMR_REQUIRE(x && pos && y && rows >= 0 && l > 0 && c > 0, "mmr_x3_add_pos: bad arguments");
   if (rows == 0) return MMR_OK;
-  if (c % 4 == 0 && al16(x) && al16(pos) && al16(y))
+  if (c % 4 == 0 && aligned16(x) && aligned16(pos) && aligned16(y))
     x3_add_pos4<<<dim3((unsigned)mmr::ceil_div(rows * (c / 4), 256)), 256, 0, mmr::as_stream(stream)>>>(x, pos, y, rows,
                                                                                                        l, c);
   else
@@ -1037,8 +1031,8 @@ mmr_status mmr_x3_add_pos_split(const float* x, const float* pos, float* y, uint
                                 int32_t c, void* stream) {
   mmr::clear_error();
   const int kp = mmr_x3_p8_kpad(c);
-  MMR_REQUIRE(x && pos && xs && rows >= 0 && l > 0 && c > 0 && c % 4 == 0 && kp > 0 && al16(x) && al16(pos) &&
-                  (!y || al16(y)) && al16(xs),
+  MMR_REQUIRE(x && pos && xs && rows >= 0 && l > 0 && c > 0 && c % 4 == 0 && kp > 0 && aligned16(x) && aligned16(pos) &&
+                  (!y || aligned16(y)) && aligned16(xs),
               "mmr_x3_add_pos_split: bad arguments (c %% 4 == 0, c <= 4096, 16-B aligned; c=%d)", c);
   if (rows == 0) return MMR_OK;
   x3_add_pos_split<<<dim3((unsigned)mmr::ceil_div(rows * (kp / 4), 256)), 256, 0, mmr::as_stream(stream)>>>(
@@ -1051,8 +1045,8 @@ mmr_status mmr_x3_assemble_seq_split(const float* x1, const float* patches_fused
                                      uint16_t* xs, int32_t b, int32_t np, int32_t c, void* stream) {
   mmr::clear_error();
   const int kp = mmr_x3_p8_kpad(c);
-  MMR_REQUIRE(x1 && patches_fused && x2 && pe && xs && b >= 0 && np > 0 && c > 0 && c % 4 == 0 && kp > 0 && al16(x1) &&
-                  al16(patches_fused) && al16(x2) && al16(pe) && al16(xs),
+  MMR_REQUIRE(x1 && patches_fused && x2 && pe && xs && b >= 0 && np > 0 && c > 0 && c % 4 == 0 && kp > 0 && aligned16(x1) &&
+                  aligned16(patches_fused) && aligned16(x2) && aligned16(pe) && aligned16(xs),
               "mmr_x3_assemble_seq_split: bad arguments (c %% 4 == 0, c <= 4096, 16-B aligned; c=%d)", c);
   if (b == 0) return MMR_OK;
   const int64_t n4 = (int64_t)b * (np + 2) * (kp / 4);
@@ -1068,7 +1062,7 @@ mmr_status mmr_x3_assemble_seq(const float* x1, const float* patches_fused, cons
   MMR_REQUIRE(x1 && patches_fused && x2 && pe && seq && b >= 0 && np > 0 && c > 0, "mmr_x3_assemble_seq: bad arguments");
   if (b == 0) return MMR_OK;
   const int64_t n = (int64_t)b * (np + 2) * c;
-  if (c % 4 == 0 && al16(x1) && al16(patches_fused) && al16(x2) && al16(pe) && al16(seq))
+  if (c % 4 == 0 && aligned16(x1) && aligned16(patches_fused) && aligned16(x2) && aligned16(pe) && aligned16(seq))
     x3_assemble_seq4<<<dim3((unsigned)mmr::ceil_div(n / 4, 256)), 256, 0, mmr::as_stream(stream)>>>(
         x1, patches_fused, x2, pe, seq, b, np, c);
   else

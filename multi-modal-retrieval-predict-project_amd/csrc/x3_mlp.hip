@@ -22,12 +22,14 @@
 
 namespace {
 
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+using mmr::aligned16;
+using mmr::bf16x8;
+using mmr::f32x16;
+using mmr::f32x4;
+using mmr::LGKM0;
+using mmr::split2;
+using mmr::vmcnt_n;
 typedef __attribute__((address_space(3))) void* lds_ptr_t;
-
-constexpr int vmcnt_n(int n) { return (n & 15) | (7 << 4) | (15 << 8) | ((n >> 4) << 14); }
 
 template <int C, int NW, int HC, int R>
 struct X3MlpGeo {
@@ -67,18 +69,6 @@ __global__ __launch_bounds__(256) void x3_swin_mlp_pack(const float* __restrict_
   }
   const uint16_t hi = mmr::f2bf(v);
   pack[(int64_t)ch * CE + part * W1E + dst] = (part & 1) ? mmr::f2bf(v - mmr::bf2f(hi)) : hi;
-}
-
-// GELU(erf) with erf by Abramowitz-Stegun 7.1.26 (mmr::gelu_erf: |erf err| <= 1.5e-7, one v_exp + one
-// v_rcp, branch-free): the GELU's absolute error <= 0.75e-7 |x|, 100x below the x3 products' 2^-17.  ocml
-// erff (a branchy polynomial) made the kernel VALU-bound: stage 1 615 vs 529 us, stage 2 587 vs 464 us at
-// B = 256, the same max deviation from the unfused chain (profiles/r05_x3_mlp_ab.txt)
-__device__ __forceinline__ float gelu_exact(float v) { return mmr::gelu_erf(v); }
-
-// two f32 -> (hi, lo) packed bf16 pairs
-__device__ __forceinline__ void split2(float a, float b, uint32_t& hi, uint32_t& lo) {
-  hi = mmr::pack2bf(a, b);
-  lo = mmr::pack2bf(a - __uint_as_float(hi << 16), b - __uint_as_float(hi & 0xFFFF0000u));
 }
 
 template <int C, int NW, int HC, int R>
@@ -121,7 +111,7 @@ __global__ __launch_bounds__(64 * NW) void x3_swin_mlp(const float* __restrict__
   stage(0);
   if constexpr (R == 3) stage(1);
   __builtin_amdgcn_s_waitcnt(vmcnt_n((R - 1) * G::PW));  // x and chunk 0 landed
-  __builtin_amdgcn_s_waitcnt(0xC07F);                    // lgkmcnt(0): parameter stores landed
+  __builtin_amdgcn_s_waitcnt(LGKM0);                     // lgkmcnt(0): parameter stores landed
   asm volatile("" ::: "memory");
   __builtin_amdgcn_s_barrier();
   asm volatile("" ::: "memory");
@@ -197,8 +187,8 @@ __global__ __launch_bounds__(64 * NW) void x3_swin_mlp(const float* __restrict__
       uint32_t hph[8], hpl[8];
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
-        split2(gelu_exact(a1[4 * i]), gelu_exact(a1[4 * i + 1]), hph[2 * i], hpl[2 * i]);
-        split2(gelu_exact(a1[4 * i + 2]), gelu_exact(a1[4 * i + 3]), hph[2 * i + 1], hpl[2 * i + 1]);
+        split2(mmr::gelu_erf(a1[4 * i]), mmr::gelu_erf(a1[4 * i + 1]), hph[2 * i], hpl[2 * i]);
+        split2(mmr::gelu_erf(a1[4 * i + 2]), mmr::gelu_erf(a1[4 * i + 3]), hph[2 * i + 1], hpl[2 * i + 1]);
       }
 #pragma unroll
       for (int s2 = 0; s2 < 2; ++s2) {  // k-step over hidden 32 t + 16 s2 .. + 15
@@ -238,7 +228,7 @@ __global__ __launch_bounds__(64 * NW) void x3_swin_mlp(const float* __restrict__
       for (int rr = 0; rr < 4; ++rr) v[rr] = acc2[u][4 * i + rr] + bb[rr];
       *(f32x4*)(sw + r * 36 + 8 * i + 4 * h) = v;
     }
-    __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0): the slice is in LDS
+    __builtin_amdgcn_s_waitcnt(LGKM0);  // lgkmcnt(0): the slice is in LDS
     __builtin_amdgcn_wave_barrier();
 #pragma unroll
     for (int k = 0; k < 4; ++k) {  // lane: token 8 k + lane / 8, channels 4 (lane % 8) .. + 3 of the slice
@@ -249,7 +239,7 @@ __global__ __launch_bounds__(64 * NW) void x3_swin_mlp(const float* __restrict__
         *(f32x4*)(y + o) = *(const f32x4*)(sw + t * 36 + c4) + xq;
       }
     }
-    __builtin_amdgcn_s_waitcnt(0xC07F);
+    __builtin_amdgcn_s_waitcnt(LGKM0);
     __builtin_amdgcn_wave_barrier();
   }
 }
@@ -338,7 +328,7 @@ __global__ __launch_bounds__(64 * NW) void x3_rowlin(const float* __restrict__ x
   stage(0);
   if constexpr (R == 3) stage(1);
   __builtin_amdgcn_s_waitcnt(vmcnt_n((R - 1) * G::PW));  // x and chunk 0 landed
-  __builtin_amdgcn_s_waitcnt(0xC07F);
+  __builtin_amdgcn_s_waitcnt(LGKM0);
   asm volatile("" ::: "memory");
   __builtin_amdgcn_s_barrier();
   asm volatile("" ::: "memory");
@@ -574,7 +564,7 @@ __global__ __launch_bounds__(64 * NW, 4) void x3_patch_embed_ln(const float* __r
         for (int rr = 0; rr < 4; ++rr) v[rr] = (acc[u][4 * i + rr] - mean) * rstd * g4[rr] + b4[rr];
         *(f32x4*)(sw + r * 36 + 8 * i + 4 * h) = v;
       }
-      __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0): the slice is in LDS
+      __builtin_amdgcn_s_waitcnt(LGKM0);  // lgkmcnt(0): the slice is in LDS
       __builtin_amdgcn_wave_barrier();
       if constexpr (X3) {  // lane: token 8 k + lane / 8, channels 4 (lane % 8) .. + 3 of the slice
 #pragma unroll
@@ -592,7 +582,7 @@ __global__ __launch_bounds__(64 * NW, 4) void x3_patch_embed_ln(const float* __r
                          mmr::pack2bf(b2[2], b2[3]));
         }
       }
-      __builtin_amdgcn_s_waitcnt(0xC07F);  // this slice's reads done before the next slice's writes
+      __builtin_amdgcn_s_waitcnt(LGKM0);  // this slice's reads done before the next slice's writes
       __builtin_amdgcn_wave_barrier();
     }
   }
@@ -619,7 +609,7 @@ mmr_status mmr_x3_swin_mlp(const float* x, const float* ln_g, const float* ln_b,
   mmr::clear_error();
   MMR_REQUIRE(x && ln_g && ln_b && pack && b1 && b2 && y, "mmr_x3_swin_mlp: NULL pointer");
   MMR_REQUIRE(tokens >= 0 && x != y, "mmr_x3_swin_mlp: tokens < 0 or in place");
-  MMR_REQUIRE(((uintptr_t)x & 15) == 0 && ((uintptr_t)y & 15) == 0 && ((uintptr_t)b2 & 15) == 0,
+  MMR_REQUIRE(aligned16(x) && aligned16(y) && aligned16(b2),
               "mmr_x3_swin_mlp: x / y / b2 must be 16-B aligned");
   if (tokens == 0) return MMR_OK;
   hipStream_t st = mmr::as_stream(stream);
@@ -665,8 +655,8 @@ mmr_status mmr_x3_rowlin(const float* x, const uint16_t* xs, const float* ln_g, 
   MMR_REQUIRE(!x || (ln_g && ln_b), "mmr_x3_rowlin: f32 rows are taken with their LayerNorm");
   MMR_REQUIRE(pack && bias && y && tokens >= 0 && y != residual && (const void*)y != (const void*)x,
               "mmr_x3_rowlin: bad arguments");
-  auto al = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
-  MMR_REQUIRE(al(x) && al(xs) && al(y) && al(residual) && al(bias), "mmr_x3_rowlin: 16-B aligned pointers");
+  MMR_REQUIRE(aligned16(x) && aligned16(xs) && aligned16(y) && aligned16(residual) && aligned16(bias),
+              "mmr_x3_rowlin: 16-B aligned pointers");
   MMR_REQUIRE(c != 96 || n > 64, "mmr_x3_rowlin: c=96 takes n > 64 (its 3-deep weight ring)");
   if (tokens == 0) return MMR_OK;
   hipStream_t st = mmr::as_stream(stream);
@@ -700,8 +690,9 @@ static mmr_status patch_embed_ln(const char* who, bool x3, const float* img, int
   MMR_REQUIRE(img && pack && bias && ln_g && ln_b && y, "%s: NULL pointer", who);
   MMR_REQUIRE(b >= 0 && hw > 0 && hw % 4 == 0 && ((hw / 4) * (hw / 4)) % 32 == 0,
               "%s: b=%d hw=%d (hw %% 4 == 0, (hw/4)^2 %% 32 == 0)", who, b, hw);
-  auto al = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
-  MMR_REQUIRE(al(img) && al(y) && al(bias) && al(ln_g) && al(ln_b) && al(pack), "%s: 16-B aligned pointers", who);
+  MMR_REQUIRE(aligned16(img) && aligned16(y) && aligned16(bias) && aligned16(ln_g) && aligned16(ln_b) &&
+                  aligned16(pack),
+              "%s: 16-B aligned pointers", who);
   if (b == 0) return MMR_OK;
   const int64_t ntile = (int64_t)b * (hw / 4) * (hw / 4) / 32;
   const int64_t grid = std::min<int64_t>(2048, mmr::ceil_div(ntile, 4));

@@ -29,12 +29,15 @@
 
 namespace {
 
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
+using mmr::bf16x8;
+using mmr::cu_count;
+using mmr::f32x16;
+using mmr::f32x4;
+using mmr::half_max;
+using mmr::half_sum;
+using mmr::mfma3;
+using mmr::vmcnt_n;
 typedef __attribute__((address_space(3))) void* lds_ptr_t;
-
-constexpr int vmcnt_n(int n) { return (n & 15) | (7 << 4) | (15 << 8) | ((n >> 4) << 14); }
 
 constexpr int SC = 96, SNH = 3, SWS = 7, STOK = 49, SKS = SC / 16;
 constexpr int S_QKV_E = 3 * SC * SC;  // bf16 elements of one qkv image
@@ -86,7 +89,10 @@ __global__ __launch_bounds__(256) void x3_sab_pack(const float* __restrict__ qkv
   }
 }
 
-// 16 f32 accumulators -> (hi, lo) fragments of k-step s (values 8 s .. 8 s + 7)
+// 16 f32 accumulators -> (hi, lo) fragments of k-step s (values 8 s .. 8 s + 7).  mmr::split2's arithmetic, spelled
+// out: through mmr::split2 hipcc contracts other multiplies into the v - hi subtractions (tools/isa_diff.py: v_fma_f32
+// 54 -> 100, v_sub_f32 540 -> 150) and the block's output moves in the last bits (tools/x3_sab_ab.py on an MI355X:
+// max deviation from the unfused chain 1.87e-6 -> 1.93e-6)
 __device__ __forceinline__ void split_frag(const f32x16& a, int s, bf16x8& hi, bf16x8& lo) {
   uint32_t h[4], l[4];
 #pragma unroll
@@ -97,21 +103,6 @@ __device__ __forceinline__ void split_frag(const f32x16& a, int s, bf16x8& hi, b
   }
   hi = __builtin_bit_cast(bf16x8, make_uint4(h[0], h[1], h[2], h[3]));
   lo = __builtin_bit_cast(bf16x8, make_uint4(l[0], l[1], l[2], l[3]));
-}
-
-__device__ __forceinline__ f32x16 mfma3(const bf16x8 ah, const bf16x8 al, const bf16x8 bh, const bf16x8 bl, f32x16 c) {
-  c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh, c, 0, 0, 0);
-  c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl, c, 0, 0, 0);
-  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh, c, 0, 0, 0);
-}
-
-__device__ __forceinline__ float half_sum(float v) {
-  const auto p = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-  return __uint_as_float(p[0]) + __uint_as_float(p[1]);
-}
-__device__ __forceinline__ float half_max(float v) {
-  const auto p = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-  return fmaxf(__uint_as_float(p[0]), __uint_as_float(p[1]));
 }
 
 __global__ __launch_bounds__(S_NWV * 64, 1) void x3_swin_attn_block(const float* __restrict__ x,
@@ -360,17 +351,6 @@ __global__ __launch_bounds__(S_NWV * 64, 1) void x3_swin_attn_block(const float*
   }
 }
 
-int sab_cu_count() {
-  static int n = [] {
-    int dev = 0, v = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0)
-      v = 256;
-    return v;
-  }();
-  return n;
-}
-
 }  // namespace
 
 extern "C" {
@@ -407,7 +387,7 @@ mmr_status mmr_x3_swin_attn_block(const float* x, const void* pack, const float*
   const int64_t wins = (int64_t)b * (hw / SWS) * (hw / SWS);
   MMR_REQUIRE(wins < (int64_t)1 << 31 && (int64_t)b * hw * hw * SC < ((int64_t)1 << 40),
               "mmr_x3_swin_attn_block: %lld windows", (long long)wins);
-  const int64_t grid = std::min<int64_t>(sab_cu_count(), (wins + S_NWV - 1) / S_NWV);
+  const int64_t grid = std::min<int64_t>(cu_count(), (wins + S_NWV - 1) / S_NWV);
   x3_swin_attn_block<<<dim3((unsigned)grid), S_NWV * 64, S_IMG_B, mmr::as_stream(stream)>>>(
       x, (const unsigned char*)pack, bias, y, b, hw, shift, eps);
   MMR_LAUNCH_CHECK();
