@@ -100,6 +100,40 @@ mmr_status mmr_index_search(mmr_index* index, const float* q, int64_t nq, int32_
 mmr_status mmr_index_link_graph(mmr_index* index, double threshold, int32_t max_links, int64_t row0,
                                  int64_t nrows, int64_t* out_nbr, int32_t* out_cnt, void* stream);
 
+/* Batched DLS walk (DLSRetrievalEngine.retrieve without reranking, src/Retrieval/retrieval.py:198-244): nq
+ * independent greedy walks over a link graph of this index, one wavefront per query.  The reference's heap only
+ * holds a totally ordered set, so the walk is stated, and implemented, as a set algorithm:
+ *   score(i) = <g_i, q> / fma(|g_i|, |q| + 1e-6, 1e-12) in f64 (the denominator is ONE fused multiply-add): the
+ *     reference's expression, not mmr_index_search's cosine.  <g_i, q> is summed in f64 from the f32 row and query
+ *     in one fixed order (lane l of 64 takes the floats 256 c + 4 l .. + 3 of every 256-float chunk c in ascending
+ *     order, f64 FMAs; the 64 partials through the xor 32, 16, 8, 4, 2, 1 tree), |g_i| is the index's f64 row norm,
+ *     |q| the square root of the same tree's sum of the lanes' q^2 partials.  The score of a row depends on nothing
+ *     but the row and the query: not on the batch slot, the neighbour position or the rows loaded with it, so
+ *     byte-identical rows tie bit for bit.  A zero row or a zero query scores 0.
+ *   order: score descending, then LOCAL row index ascending ("best" below).
+ *   set, visited := the seeds; a seed or neighbour that is < 0, >= n or already visited is skipped (-1 padding,
+ *     garbage, self-loops, a row listed twice).
+ *   while steps < max_steps and the set is not empty: remove the best row b from the set; add every unvisited
+ *     nbr[b][0 .. max_links) to visited and to the set; if the set holds more than r rows keep the best r; if no
+ *     row was added the walk stops (that step is not counted, b stays removed); else steps += 1.
+ *   output: the best min(k, |set|) rows, written in (score descending, index DESCENDING) order — the reference's
+ *     sorted(..., reverse=True) over (sim, idx) tuples: a run of equal scores that straddles the k boundary keeps
+ *     its lower indices and prints them high to low.  Slots past the set are (-1, -inf).
+ * q (nq, d) f32; nbr (n, max_links) int64 LOCAL rows as mmr_index_link_graph writes them; seeds (nq, seed_size)
+ * int64 LOCAL rows; r = the reference's R = max(candidate_multiplier * K, seed_size).  out_idx (nq, k) int64
+ * GLOBAL (+ idx_base), out_score (nq, k) f32, out_score64 (nq, k) f64 (may be NULL), out_steps / out_visited (nq)
+ * int32 (may be NULL): the counted steps and |visited|.
+ * Limits (MMR_ERR_INVALID beyond them, before any launch): 1 <= r <= 512; 1 <= max_links <= 32; 1 <= k <= r;
+ * 0 <= seed_size <= r; max_steps >= 0; min(n, seed_size + max_steps * max_links) <= 4096 (the visited set; the
+ * reference's defaults at max_links = 32 need 3205); d <= 1024; n < 2^31; nq < 2^31.  An MMR_F32 index only: a
+ * native fp16 index returns MMR_ERR_UNSUPPORTED.  All pointers device; asynchronous on `stream`, no host
+ * synchronisation, no allocation (the working sets live in LDS), no atomics on global memory: two runs give
+ * identical bytes.  nq == 0 launches nothing. */
+mmr_status mmr_index_dls_walk(const mmr_index* index, const float* q, int64_t nq, const int64_t* nbr,
+                              int32_t max_links, const int64_t* seeds, int32_t seed_size, int32_t k,
+                              int32_t max_steps, int32_t r, int64_t* out_idx, float* out_score,
+                              double* out_score64, int32_t* out_steps, int32_t* out_visited, void* stream);
+
 /* KG / label reranker fused after the top-K (Reranker.rerank, src/Retrieval/reranker.py:240-333):
  * per query the kc candidates cand (nq, kc) int64 (global indices into this index, -1 = empty,
  * kc <= 64) are re-scored with alpha*minmax(cos(q_emb, row)) + beta*minmax(Jaccard(label sets)) +

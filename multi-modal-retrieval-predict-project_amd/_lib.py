@@ -28,6 +28,8 @@ SIGNATURES = {
     "mmr_index_set_mode": [c_vp, c_i32],
     "mmr_index_search": [c_vp, c_vp, c_i64, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp],
     "mmr_index_link_graph": [c_vp, ctypes.c_double, c_i32, c_i64, c_i64, c_vp, c_vp, c_vp],
+    "mmr_index_dls_walk": [c_vp, c_vp, c_i64, c_vp, c_i32, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp,
+                           c_vp, c_vp],
     "mmr_index_rerank": [c_vp, c_vp, c_i64, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_i32, ctypes.c_double,
                          ctypes.c_double, ctypes.c_double, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp],
     "mmr_merge_topk": [c_vp, c_vp, c_i32, c_i64, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp],

@@ -6,7 +6,8 @@ MI355XRetrievalEngine      exact brute-force cosine top-K on the GPU (libmmr, in
                            cosine of the raw rows, descending; ties -> lower gallery index.
 DLSRetrievalEngine         retrieval.py:53-271: link graph = exact GPU self-join (SURVEY.md §8f row
                            2); the approximate random-seeded greedy walk (3.75 % recall@10 vs exact in
-                           the survey probe, §8a-a11) stays the reference's host algorithm.
+                           the survey probe, §8a-a11): retrieve() is the reference's host algorithm,
+                           retrieve_batch() the same walk for a batch on the device (mmr_index_dls_walk).
 make_retrieval_engine      retrieval.py:273-304  (string switch; unknown method -> ValueError)
 """
 import abc
@@ -184,6 +185,41 @@ class GalleryIndex:
                                                        _lib.ptr(nbr[r0:]), _lib.ptr(cnt[r0:]), _lib.stream_ptr(dev)),
                        "mmr_index_link_graph")
         return nbr, cnt
+
+    def dls_walk(self, q, nbr, seeds, k: int, max_steps: int = 100, r=None, want_f64: bool = False,
+                 want_stats: bool = False):
+        """Batched DLS walk (mmr_index_dls_walk; retrieval.py:198-244 per query).  q (B, D) f32 device tensor;
+        nbr (n, max_links) int64 LOCAL rows, -1 padded (link_graph's layout); seeds (B, seed_size) int64 LOCAL
+        rows; r = the reference's R (default max(10 k, seed_size)).  -> (idx int64 (B,k) global, -1 past the
+        set; score f32 (B,k), -inf there [, score64][, steps int32 (B,), visited int32 (B,)])."""
+        _lib.require_gpu(q)
+        if q.dim() != 2 or q.shape[1] != self.d:
+            raise ValueError(f"query shape {tuple(q.shape)} does not match gallery dim {self.d}")
+        B, dev = q.shape[0], q.device
+        if nbr.dim() != 2 or nbr.shape[0] != self.n:
+            raise ValueError(f"neighbour table {tuple(nbr.shape)} does not match the index's {self.n} rows")
+        if seeds.dim() != 2 or seeds.shape[0] != B:
+            raise ValueError(f"seeds {tuple(seeds.shape)} do not match {B} queries")
+        q = q.to(torch.float32).contiguous()
+        nbr = nbr.to(dev, torch.int64).contiguous()
+        seeds = seeds.to(dev, torch.int64).contiguous()
+        k, seed_size = int(k), int(seeds.shape[1])
+        r = max(10 * k, seed_size) if r is None else int(r)
+        idx = torch.empty((B, k), dtype=torch.int64, device=dev)
+        sc = torch.empty((B, k), dtype=torch.float32, device=dev)
+        sc64 = torch.empty((B, k), dtype=torch.float64, device=dev) if want_f64 else None
+        st = torch.empty((B,), dtype=torch.int32, device=dev) if want_stats else None
+        vis = torch.empty((B,), dtype=torch.int32, device=dev) if want_stats else None
+        _lib.check(_lib.lib().mmr_index_dls_walk(self._h, _lib.ptr(q), B, _lib.ptr(nbr), int(nbr.shape[1]),
+                                                 _lib.ptr(seeds), seed_size, k, int(max_steps), r, _lib.ptr(idx),
+                                                 _lib.ptr(sc), _lib.ptr(sc64), _lib.ptr(st), _lib.ptr(vis),
+                                                 _lib.stream_ptr(dev)), "mmr_index_dls_walk")
+        out = [idx, sc]
+        if want_f64:
+            out.append(sc64)
+        if want_stats:
+            out += [st, vis]
+        return tuple(out)
 
     def rerank(self, q_emb, cand, q_labels, g_labels, q_kg, g_kg, topk, alpha=0.6, beta=0.25, gamma=0.15,
                want_components=True):
@@ -456,7 +492,8 @@ class DLSRetrievalEngine(MI355XRetrievalEngine):
     (mmr_index_link_graph: the row itself excluded, score >= link_threshold, first max_links by
     score desc / index asc).  The query-time greedy walk (retrieval.py:140-271) is the reference's
     sequential, approximate host algorithm (random seeds, a (-sim, idx) heap, the visited set) and
-    runs here exactly as there; exact retrieval is MI355XRetrievalEngine.search.
+    runs in retrieve() exactly as there; retrieve_batch() runs the same walk, as a set algorithm over the
+    total order (-sim, idx), for a whole batch on the device; exact retrieval is MI355XRetrievalEngine.search.
     The graph cache is an .npz (offsets + flat neighbours + dim), never a pickle."""
 
     def __init__(self, features_path: Optional[str] = None, ids_path: Optional[str] = None,
@@ -517,9 +554,73 @@ class DLSRetrievalEngine(MI355XRetrievalEngine):
         np.savez(self.fdb_path, offsets=off, flat=flat, dim=np.int64(self.embs.shape[1]))
 
     def _build_link_graph(self, threshold: float, max_links: int) -> List[List[int]]:
-        nbr, cnt = self.index.link_graph(threshold, max_links)
-        nbr, cnt = nbr.cpu().numpy(), cnt.cpu().numpy()
-        return [nbr[i, :cnt[i]].tolist() for i in range(len(cnt))]
+        nbr_dev, cnt = self.index.link_graph(threshold, max_links)
+        nbr, cnt = nbr_dev.cpu().numpy(), cnt.cpu().numpy()
+        graph = [nbr[i, :cnt[i]].tolist() for i in range(len(cnt))]
+        self._nbr_cache = (graph, nbr_dev)  # the device table of exactly this list: retrieve_batch does not upload it again
+        return graph
+
+    def _device_graph(self):
+        """(n, width) int64 device neighbour table, -1 padded, of whatever self.link_graph currently is (width =
+        its longest row, at least 1); cached by the list's identity, so assigning another graph takes effect."""
+        cached = getattr(self, "_nbr_cache", None)
+        if cached is not None and cached[0] is self.link_graph:
+            return cached[1]
+        graph = self.link_graph
+        width = max(1, max((len(x) for x in graph), default=0))
+        tab = np.full((len(graph), width), -1, np.int64)
+        for i, x in enumerate(graph):
+            tab[i, :len(x)] = x
+        nbr_dev = torch.from_numpy(tab).to(f"cuda:{self.device}")
+        self._nbr_cache = (graph, nbr_dev)
+        return nbr_dev
+
+    def draw_seeds(self, B: int, seed_size: int = 5, seed=None, query_ids=None):
+        """(B, min(seed_size, N)) int64 seed rows, drawn per query exactly as retrieve() draws them:
+        RandomState(s).choice(N, size, replace=False) is the stream of np.random.seed(s); np.random.choice(...),
+        without touching numpy's global state.  s = seed (an int, or B ints), else the query id's process-salted
+        hash, else fresh entropy."""
+        N = self.embs.shape[0]
+        if seed is not None:
+            ss = [int(seed)] * B if np.ndim(seed) == 0 else [int(s) for s in seed]
+        elif query_ids is not None:
+            ss = [abs(hash(str(x))) % (2 ** 32) for x in query_ids]
+        else:
+            ss = [None] * B
+        if len(ss) != B:
+            raise ValueError(f"{len(ss)} seeds / query_ids for {B} queries")
+        n_s = min(int(seed_size), N)
+        out = np.empty((B, n_s), np.int64)
+        for b, s in enumerate(ss):
+            out[b] = np.random.RandomState(s).choice(N, size=n_s, replace=False)
+        return out
+
+    def retrieve_batch(self, Q, K: int = 5, seed_size: int = 5, max_steps: int = 100, candidate_multiplier: int = 10,
+                       seeds=None, seed=None, query_ids=None, return_stats: bool = False):
+        """The walk of retrieve() for a whole batch on the device (mmr_index_dls_walk), without reranking: Q (B, D)
+        -> (idx (B, K) int64 gallery rows, scores (B, K) f32) in retrieve()'s order, (-1, -inf) past a walk's
+        candidate set; with return_stats also (steps (B,), visited (B,)) int32.  Device tensors for torch input,
+        numpy otherwise.  seeds: explicit (B, seed_size) rows; else drawn by draw_seeds(seed / query_ids)."""
+        N = self.embs.shape[0]
+        if len(self.link_graph) != N:
+            raise RuntimeError(f"Link graph size {len(self.link_graph)} != embeddings {N}. Rebuild or delete "
+                               f"your cache.")
+        is_np = not isinstance(Q, torch.Tensor)
+        q = torch.as_tensor(np.asarray(Q, np.float32) if is_np else Q)
+        if q.dim() == 1:
+            q = q[None]
+        dev = f"cuda:{self.device}"
+        q = q.to(dev, torch.float32)
+        B = q.shape[0]
+        if seeds is None:
+            seeds = self.draw_seeds(B, seed_size, seed, query_ids)
+        seeds = torch.as_tensor(np.asarray(seeds, np.int64) if not isinstance(seeds, torch.Tensor) else seeds)
+        if seeds.dim() != 2 or seeds.shape[0] != B:
+            raise ValueError(f"seeds {tuple(seeds.shape)} for {B} queries: expected (B, seed_size)")
+        R = max(int(candidate_multiplier) * int(K), int(seed_size), int(seeds.shape[1]))
+        out = self.index.dls_walk(q, self._device_graph(), seeds.to(dev), int(K), max_steps=max_steps, r=R,
+                                  want_stats=return_stats)
+        return tuple(t.cpu().numpy() for t in out) if is_np else out
 
     def retrieve(self, query_emb, K: int = 5, seed_size: int = 5, max_steps: int = 100,
                  candidate_multiplier: int = 10, reranker=None, query_id=None, rerank_topk=None,
