@@ -229,6 +229,38 @@ mmr_status mmr_index_count_ahead(const mmr_index* index, const float* q, int64_t
                                  const double* ref_score, const int64_t* exclude, int64_t* out_ahead, void* work,
                                  void* stream);
 
+/* Retrieval diversity of retrieved lists (compute_embedding_diversity / compute_label_diversity_from_labels,
+ * src/Evaluate/retrieval_diversity_compute.py:171-194), for nq lists at once.  idx (nq, k) int64 holds GLOBAL
+ * indices as mmr_index_search, mmr_index_dls_walk and mmr_index_rerank write them.  For one list idx[q][0 .. k):
+ *   valid: an entry is valid iff idx_base <= idx < idx_base + n; every other entry is skipped (the -1 padding of
+ *     walks and short galleries, garbage: the reference's `if r in id_to_emb`).  m = the number of valid entries.
+ *     A row listed twice counts twice; its pair with itself elsewhere in the list is an ordinary pair.
+ *   cosine: c(i, j) = <g_i, g_j> / (max(|g_i|, 1e-8) * max(|g_j|, 1e-8)) in f64 of the raw rows (fp16 rows upcast
+ *     exactly), |g| = the index's f64 row norm.  The 1e-8 clip is the reference's norms.clip(min=1e-8), NOT
+ *     mmr_index_search's "0 when a norm is 0": a zero row gives 0 either way, a row whose norm is below 1e-8 gives a
+ *     shrunken, nonzero cosine (two rows of 1e-9 at d = 4: diversity 0.96).
+ *   out_emb[q] = (m < 2) ? 0.0 : 1 - (sum over valid list positions i < j of c(i, j)) / (m (m - 1) / 2).  The sum
+ *     runs in one fixed order that depends on the list's own contents and k only — never on nq, the batch slot or
+ *     neighbouring lists (csrc/list_div.hip states it).  No atomics: two runs give identical bytes.
+ *   labels (g_labels (n) uint64 bitsets in local row order, as mmr_index_rerank's): over the valid entries
+ *     u = popcount(OR of the bitsets), s = sum of the popcounts, c = the number of entries with a non-empty bitset;
+ *     out_lab[q] = (c == 0) ? 0.0 : (double)u / ((double)s / (double)c) — two f64 divisions in this order,
+ *     contraction off: the reference's len(all_labels) / float(np.mean(sizes_nonzero)) bit for bit.
+ *     g_labels and out_lab are both NULL or both set.
+ *   out_valid (nq) int32 = m; may be NULL.
+ *   out_sim (nq, k, k) f64, may be NULL: c(i, j) at the list positions, the diagonal included, from the same
+ *     expression; every row and column of an invalid entry is 0.0; (i, j) and (j, i) hold the same bits.
+ * Limits (MMR_ERR_INVALID beyond them, before any launch): 1 <= k <= mmr_max_k() (256); nq >= 0 (nq == 0 launches
+ * nothing); idx and out_emb non-NULL.  Both index kinds (MMR_F32, MMR_F16).  work:
+ * mmr_index_list_diversity_work_bytes(index, nq, k) bytes of scratch owned by the caller, 16-B aligned (0 bytes,
+ * and work may be NULL, for k <= 16: one wavefront finishes such a list; beyond, per-tile-pair partial sums pass
+ * through it).  The index is const: its search workspace is not touched.  All pointers device, asynchronous on
+ * `stream`, no host synchronisation, no allocation. */
+int64_t mmr_index_list_diversity_work_bytes(const mmr_index* index, int64_t nq, int32_t k);
+mmr_status mmr_index_list_diversity(const mmr_index* index, const int64_t* idx, int64_t nq, int32_t k,
+                                    const uint64_t* g_labels, double* out_emb, double* out_lab, int32_t* out_valid,
+                                    double* out_sim, void* work, void* stream);
+
 /* ---------------------------------------------------------------- tower ops (bf16 = uint16) */
 /* Y[m][n] = act(X[m][k] . W[n][k]^T + bias[n]) (+ R[m][n]); X, W, R, Y bf16; bias f32 or NULL;
  * act: 0 none, 1 GELU(erf).  nn.Linear semantics (weight [out][in]).  f32 accumulation. */

@@ -40,6 +40,8 @@ SIGNATURES = {
     "mmr_index_rank_work_bytes": [c_vp, c_i64],
     "mmr_index_best_relevant": [c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp],
     "mmr_index_count_ahead": [c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp],
+    "mmr_index_list_diversity_work_bytes": [c_vp, c_i64, c_i32],
+    "mmr_index_list_diversity": [c_vp, c_vp, c_i64, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp],
     "mmr_rerank_mix": [c_vp, c_vp, c_i64, c_i32, ctypes.c_double, ctypes.c_double, ctypes.c_double, c_i32, c_vp, c_vp,
                        c_vp, c_vp, c_vp, c_vp],
     "mmr_linear_bf16": [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i32, c_i32, c_i32, c_vp],
@@ -151,7 +153,8 @@ _RESTYPES = {"mmr_last_error": ctypes.c_char_p, "mmr_version": ctypes.c_int, "mm
              "mmr_x3_patch_embed_pack_elems": ctypes.c_int64,
              "mmr_x3_swin_attn_block_pack_bytes": ctypes.c_int64,
              "mmr_classifier_pack_bytes": ctypes.c_int64, "mmr_classifier_work_bytes": ctypes.c_int64,
-             "mmr_index_rank_work_bytes": ctypes.c_int64, "mmr_cls_eval_work_bytes": ctypes.c_int64}
+             "mmr_index_rank_work_bytes": ctypes.c_int64, "mmr_cls_eval_work_bytes": ctypes.c_int64,
+             "mmr_index_list_diversity_work_bytes": ctypes.c_int64}
 
 ABI_VERSION = 2  # mmr_version() this binding is written against (2: the full-ranking evaluation entry points)
 

@@ -19,6 +19,10 @@ the per-query relevant count (recall's and AP's denominator) -> P@k, R@k, AP@k, 
 `classification_metrics` / `find_best_thresholds` are the classifier's evaluation
 (src/Evaluate/eval_on_test.py: per-class AUROC, AP, best-F1 thresholds, precision / recall / F1, macro
 and micro aggregates) from the exact sums ops.cls_eval computes on the device.
+`compute_embedding_diversity` / `compute_label_diversity_from_labels` are the host mirrors of
+src/Evaluate/retrieval_diversity_compute.py:171-194 in f64 (the device computes them for whole batches of
+lists: GalleryIndex.list_diversity, the engines' diversity()); `diversity_summary` is one metric's row of
+its summary_all_metrics (:142-166).
 """
 import math
 
@@ -288,3 +292,50 @@ def find_best_thresholds(y_true, y_score):
     if flags[1] != 0:
         raise ValueError("find_best_thresholds: labels must be 0 or 1")
     return thr
+
+
+def compute_embedding_diversity(embeddings):
+    """1 - mean pairwise cosine of the rows (retrieval_diversity_compute.py:171-182), in f64: norms clipped at
+    1e-8, the mean over the i < j pairs; None or fewer than 2 rows -> 0.0."""
+    if embeddings is None or len(embeddings) < 2:
+        return 0.0
+    e = np.asarray(embeddings, np.float64)
+    normed = e / np.linalg.norm(e, axis=1, keepdims=True).clip(min=1e-8)
+    sim = normed @ normed.T
+    return float(1.0 - float(np.mean(sim[np.triu_indices(sim.shape[0], k=1)])))
+
+
+def compute_label_diversity_from_labels(labels_list):
+    """Distinct labels of the list / mean label count of its labelled items (retrieval_diversity_compute.py:184-194);
+    an empty list or only empty label sets -> 0.0."""
+    if not labels_list:
+        return 0.0
+    all_labels = set(l for lab in labels_list for l in lab)
+    sizes_nonzero = [len(lab) for lab in labels_list if len(lab) > 0]
+    if not sizes_nonzero:
+        return 0.0
+    return float(len(all_labels) / float(np.mean(sizes_nonzero)))
+
+
+def diversity_summary(values):
+    """summary_all_metrics' columns (retrieval_diversity_compute.py:142-166) for one metric's per-query values
+    (a device tensor costs one host sync; numpy and lists as they are): mean, std (the SAMPLE std, ddof = 1, as
+    pandas; NaN with fewer than 2 values), median, min, max over the non-NaN values (NaN when there are none),
+    count_nonnull, total_rows, pct_missing.  NaN and None count as missing."""
+    if isinstance(values, torch.Tensor):
+        v = values.detach().to("cpu", torch.float64).numpy().reshape(-1)
+    elif isinstance(values, np.ndarray) and values.dtype.kind in "fiu":
+        v = values.astype(np.float64).reshape(-1)
+    else:
+        v = np.array([np.nan if x is None else x for x in np.asarray(values, dtype=object).reshape(-1)], np.float64)
+    total = int(v.shape[0])
+    ok = v[~np.isnan(v)]
+    cnt = int(ok.shape[0])
+    nan = float("nan")
+    return {"mean": float(ok.mean()) if cnt > 0 else nan,
+            "std": float(ok.std(ddof=1)) if cnt > 1 else nan,
+            "median": float(np.median(ok)) if cnt > 0 else nan,
+            "min": float(ok.min()) if cnt > 0 else nan,
+            "max": float(ok.max()) if cnt > 0 else nan,
+            "count_nonnull": cnt, "total_rows": total,
+            "pct_missing": 100.0 * (1.0 - cnt / total) if total > 0 else nan}

@@ -8,6 +8,8 @@ DLSRetrievalEngine         retrieval.py:53-271: link graph = exact GPU self-join
                            2); the approximate random-seeded greedy walk (3.75 % recall@10 vs exact in
                            the survey probe, §8a-a11): retrieve() is the reference's host algorithm,
                            retrieve_batch() the same walk for a batch on the device (mmr_index_dls_walk).
+                           Both engines' diversity(): retrieval_diversity_compute.py's per-query numbers for a
+                           batch of retrieved lists on the device (mmr_index_list_diversity).
 make_retrieval_engine      retrieval.py:273-304  (string switch; unknown method -> ValueError)
 """
 import abc
@@ -300,6 +302,42 @@ class GalleryIndex:
         ahead = self.count_ahead(q, idx, sc, exclude)
         return torch.where(idx >= 0, ahead + 1, torch.zeros_like(ahead)), nrel, idx, sc
 
+    # ---- retrieval diversity of retrieved lists (mmr_index_list_diversity) ----
+    def list_diversity(self, idx, g_bits=None, want_sim: bool = False):
+        """compute_embedding_diversity / compute_label_diversity_from_labels (retrieval_diversity_compute.py:171-194)
+        of B retrieved lists at once.  idx (B, k) int64 GLOBAL indices on this index's device, as search / dls_walk /
+        rerank return them; an entry outside [idx_base, idx_base + n) (the -1 padding) is skipped.  g_bits (n,) label
+        bitsets of this index's rows (numpy uint64 or int64 tensor), or None.  -> (emb_div f64 (B,): 1 - mean pairwise
+        cosine of the valid rows, 0.0 with fewer than 2; label_div f64 (B,) or None: distinct labels / mean label
+        count of the labelled rows; n_valid int32 (B,) [, sim f64 (B, k, k): the cosines at list positions, 0.0 in
+        the rows and columns of skipped entries])."""
+        L = _lib.lib()
+        if not isinstance(idx, torch.Tensor) or idx.dim() != 2 or idx.dtype != torch.int64:
+            raise ValueError("list_diversity takes a 2-D int64 tensor of global indices (B, k)")
+        if not idx.is_cuda or idx.device.index != self.device:
+            raise ValueError(f"idx lives on {idx.device}, the index on cuda:{self.device}")
+        B, k = int(idx.shape[0]), int(idx.shape[1])
+        if not 1 <= k <= L.mmr_max_k():
+            raise ValueError(f"k={k} outside [1, {L.mmr_max_k()}]")
+        dev = idx.device
+        gb = None
+        if g_bits is not None:
+            gb = bits_tensor(g_bits, dev).contiguous()
+            if gb.dim() != 1 or gb.shape[0] != self.n:
+                raise ValueError(f"label bitsets {tuple(gb.shape)} do not match the index's {self.n} rows")
+        idx = idx.contiguous()
+        emb = torch.empty((B,), dtype=torch.float64, device=dev)
+        lab = torch.empty((B,), dtype=torch.float64, device=dev) if gb is not None else None
+        nv = torch.empty((B,), dtype=torch.int32, device=dev)
+        sim = torch.empty((B, k, k), dtype=torch.float64, device=dev) if want_sim else None
+        if B > 0:
+            nbytes = int(L.mmr_index_list_diversity_work_bytes(self._h, B, k))
+            work = torch.empty((nbytes,), dtype=torch.uint8, device=dev) if nbytes else None  # caller-owned scratch
+            _lib.check(L.mmr_index_list_diversity(self._h, _lib.ptr(idx), B, k, _lib.ptr(gb), _lib.ptr(emb),
+                                                  _lib.ptr(lab), _lib.ptr(nv), _lib.ptr(sim), _lib.ptr(work),
+                                                  _lib.stream_ptr(dev)), "mmr_index_list_diversity")
+        return (emb, lab, nv, sim) if want_sim else (emb, lab, nv)
+
     def close(self):
         h, self._h = getattr(self, "_h", None), None
         if h:
@@ -464,6 +502,42 @@ class MI355XRetrievalEngine(RetrievalEngine):
         first_rank, n_rel, _, _ = self.index.rank_eval(q, qb, gb, ex)
         return evaluation_summary(list_flags(idx, qb, gb), first_rank, n_rel, ks)
 
+    def _query_tensor(self, Q):
+        q = torch.as_tensor(np.asarray(Q, np.float32) if not isinstance(Q, torch.Tensor) else Q)
+        return (q[None] if q.dim() == 1 else q).to(f"cuda:{self.device}", torch.float32)
+
+    def _diversity_result(self, idx, scores, gallery_bits, return_lists):
+        """The per-query record of run_retrieval_experiment (retrieval_diversity_compute.py:335-344) for the lists
+        idx (B, k) on the device, plus summary_all_metrics' columns per metric."""
+        from .metrics import diversity_summary
+        emb, lab, nv = self.index.list_diversity(idx, gallery_bits)
+        out = {"retrieval_diversity": emb, "retrieval_label_diversity": lab, "n_valid": nv,
+               "summary": {"retrieval_diversity": diversity_summary(emb)}}
+        if lab is not None:
+            out["summary"]["retrieval_label_diversity"] = diversity_summary(lab)
+        if return_lists:
+            out["idx"], out["scores"] = idx, scores
+        return out
+
+    def diversity(self, Q, K: int = 5, gallery_bits=None, exclude_ids=None, return_lists: bool = False):
+        """How diverse the retrieved lists are (src/Evaluate/retrieval_diversity_compute.py): one search and one
+        GalleryIndex.list_diversity, nothing per query on the host.  Q (B, D); gallery_bits (N,) label bitsets (numpy
+        uint64 or device int64) or None; exclude_ids as in evaluate(): the search runs at K + 1 and the excluded row
+        is dropped on the device.  -> {"retrieval_diversity": f64 (B,) device, "retrieval_label_diversity": f64 (B,)
+        or None, "n_valid": int32 (B,), "summary": {metric: metrics.diversity_summary(...)}} and, with return_lists,
+        "idx" (B, K) / "scores" (B, K) of the lists that were measured."""
+        q = self._query_tensor(Q)
+        ex = None if exclude_ids is None else self.exclude_tensor(exclude_ids, q.shape[0], q.device)
+        k_eff = min(int(K) + (0 if ex is None else 1), len(self.ids))
+        if k_eff - (0 if ex is None else 1) < 1:
+            raise ValueError(f"K={K} leaves no list to measure over {len(self.ids)} gallery rows")
+        idx, sc, st = self.index.search(q, k_eff, want_status=True)
+        check_status(st)
+        if ex is not None:  # drop_excluded's order, applied to the scores as well
+            order = torch.argsort((idx == ex[:, None]).to(torch.int8), dim=1, stable=True)[:, :k_eff - 1]
+            idx, sc = torch.gather(idx, 1, order), torch.gather(sc, 1, order)
+        return self._diversity_result(idx, sc, gallery_bits, return_lists)
+
     def retrieve(self, query_emb, K: int = 5, reranker=None, query_id=None, rerank_topk=None, **kwargs):
         """(D,) or (1,D) query -> (top-K ids, scores) descending (retrieval.py:34-39 contract).
         With a reranker and query_id, candidates are re-scored like retrieval.py:256-269."""
@@ -621,6 +695,20 @@ class DLSRetrievalEngine(MI355XRetrievalEngine):
         out = self.index.dls_walk(q, self._device_graph(), seeds.to(dev), int(K), max_steps=max_steps, r=R,
                                   want_stats=return_stats)
         return tuple(t.cpu().numpy() for t in out) if is_np else out
+
+    def diversity(self, Q, K: int = 5, gallery_bits=None, exact: bool = False, return_lists: bool = False,
+                  **walk_kwargs):
+        """MI355XRetrievalEngine.diversity over the lists of the DLS walk — the reference's experiment retrieves
+        through this engine (retrieval_diversity_compute.py:223-236, 290, 311): retrieve_batch(Q, K, **walk_kwargs)
+        (seed_size, max_steps, candidate_multiplier, seeds, seed, query_ids), whose lists may hold -1 past a walk's
+        candidate set; those entries are skipped and n_valid tells how many rows a list had.  exact=True measures
+        the exact top-K instead (the parent's path; walk_kwargs then go to it, e.g. exclude_ids)."""
+        if exact:
+            return super().diversity(Q, K, gallery_bits, return_lists=return_lists, **walk_kwargs)
+        if walk_kwargs.get("return_stats"):
+            raise ValueError("diversity() returns the lists, not the walk statistics: call retrieve_batch for those")
+        idx, sc = self.retrieve_batch(self._query_tensor(Q), K, **walk_kwargs)
+        return self._diversity_result(idx, sc, gallery_bits, return_lists)
 
     def retrieve(self, query_emb, K: int = 5, seed_size: int = 5, max_steps: int = 100,
                  candidate_multiplier: int = 10, reranker=None, query_id=None, rerank_topk=None,
