@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include <atomic>
+#include <type_traits>
 
 #include "mmr.h"
 
@@ -52,6 +53,34 @@ struct DeviceGuard {
 };
 
 inline bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
+
+// Runtime value -> kernel template argument (host side).  f is a generic lambda that receives a
+// std::integral_constant / std::bool_constant per choice and launches kern<decltype(c)::value, ...>; only the
+// listed values are instantiated.
+// pick<V...>(v, f): f(V) for the listed V == v; false (and no call) when none matches
+template <int... Vs, class F>
+bool pick(int v, F&& f) {
+  return ((v == Vs ? (f(std::integral_constant<int, Vs>{}), true) : false) || ...);
+}
+// pick_ceil<V...>(v, f): f(V) for the first listed V >= v, else for the last one — "the smallest built width
+// that holds v" (V ascending)
+template <int... Vs, class F>
+void pick_ceil(int v, F&& f) {
+  constexpr int vs[] = {Vs...};
+  if (!((v <= Vs ? (f(std::integral_constant<int, Vs>{}), true) : false) || ...))
+    f(std::integral_constant<int, vs[sizeof...(Vs) - 1]>{});
+}
+// pick_flags(f, b0, b1, ...): f(std::true_type / std::false_type per bool)
+template <class F, class... Bs>
+void pick_flags(F&& f, bool b, Bs... bs) {
+  if constexpr (sizeof...(Bs) == 0) {
+    if (b) f(std::true_type{});
+    else f(std::false_type{});
+  } else {
+    if (b) pick_flags([&](auto... r) { f(std::true_type{}, r...); }, bs...);
+    else pick_flags([&](auto... r) { f(std::false_type{}, r...); }, bs...);
+  }
+}
 
 // MFMA operand / accumulator and wide load / store vectors (bf16 as bit patterns)
 typedef short bf16x8 __attribute__((ext_vector_type(8)));

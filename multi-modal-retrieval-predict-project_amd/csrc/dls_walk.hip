@@ -317,17 +317,11 @@ mmr_status mmr_index_dls_walk(const mmr_index* ix, const float* q, int64_t nq, c
   DeviceGuard g(ix->device);
   hipStream_t st = mmr::as_stream(stream);
   const dim3 grid((unsigned)nq);
-#define DW_LAUNCH(NC)                                                                                               \
-  dls_walk_kernel<NC><<<grid, 64, lds, st>>>(ix->gal, ix->Dp, ix->norm64, ix->n, ix->idx_base, q, ix->d, nbr,        \
-                                             max_links, seeds, seed_size, k, max_steps, r, log_h, out_idx, out_score, \
-                                             out_score64, out_steps, out_visited)
-  switch ((ix->Dp + 255) / 256) {
-    case 1: DW_LAUNCH(1); break;
-    case 2: DW_LAUNCH(2); break;
-    case 3: DW_LAUNCH(3); break;
-    default: DW_LAUNCH(4); break;
-  }
-#undef DW_LAUNCH
+  mmr::pick_ceil<1, 2, 3, 4>((int)((ix->Dp + 255) / 256), [&](auto nc) {
+    dls_walk_kernel<nc()><<<grid, 64, lds, st>>>(ix->gal, ix->Dp, ix->norm64, ix->n, ix->idx_base, q, ix->d, nbr,
+                                                 max_links, seeds, seed_size, k, max_steps, r, log_h, out_idx, out_score,
+                                                 out_score64, out_steps, out_visited);
+  });
   MMR_LAUNCH_CHECK();
   return MMR_OK;
 }

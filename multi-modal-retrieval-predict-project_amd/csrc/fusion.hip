@@ -806,24 +806,14 @@ mmr_status launch_mha(const char* who, const uint16_t* q, int64_t ldq, const uin
   hipStream_t st = mmr::as_stream(stream);
   if (mean_out && nchunk > 1)  // query chunks accumulate their partial means
     MMR_CHECK_HIP(hipMemsetAsync(mean_out, 0, sizeof(float) * (size_t)b * heads * dh, st));
-#define MMR_MHA(D)                                                                                             \
-  do {                                                                                                         \
-    if (kmask)                                                                                                 \
-      mha_small<D, true><<<grid, blk, lds, st>>>(q, ldq, k, ldk, v, ldv, out, ldo, mean_out, kmask, lq, lk,    \
-                                                 heads, dh, scale, kbs, q8, q8s);                                   \
-    else                                                                                                       \
-      mha_small<D, false><<<grid, blk, lds, st>>>(q, ldq, k, ldk, v, ldv, out, ldo, mean_out, nullptr, lq, lk, \
-                                                  heads, dh, scale, kbs, q8, q8s);                                  \
-  } while (0)
-  switch (dt) {
-    case 1: MMR_MHA(1); break;
-    case 2: MMR_MHA(2); break;
-    case 3: MMR_MHA(3); break;
-    case 4: MMR_MHA(4); break;
-    case 5: MMR_MHA(5); break;
-    default: MMR_MHA(6); break;
-  }
-#undef MMR_MHA
+  mmr::pick_ceil<1, 2, 3, 4, 5, 6>(dt, [&](auto d) {
+    mmr::pick_flags(
+        [&](auto masked) {
+          mha_small<decltype(d)::value, masked()><<<grid, blk, lds, st>>>(q, ldq, k, ldk, v, ldv, out, ldo, mean_out,
+                                                                          kmask, lq, lk, heads, dh, scale, kbs, q8, q8s);
+        },
+        kmask != nullptr);
+  });
   MMR_LAUNCH_CHECK();
   return MMR_OK;
 }
@@ -919,21 +909,16 @@ mmr_status mmr_ln_rows(const void* x, int64_t ldx, const float* alpha, const voi
   // the scalar forms load ceil(c / 64) channels per lane (NI), not 16: at c = 96 / 192 the clamped
   // duplicate loads of a fixed 16 were most of the instructions
   const int ni = (c + 63) / 64;
-#define LNS(TI_, NI_)                                                                                            \
-  ln_rows<TI_, TI_, NI_><<<grid, 256, 0, st>>>((const TI_*)x, ldx, alpha, (const TI_*)residual, ldr, gamma, beta, \
-                                               post, ldp, post_scale, (TI_*)y, ldy, rows, c, eps, groups, group_div)
-#define LNS_DISPATCH(TI_)                        \
-  do {                                           \
-    if (ni <= 2) LNS(TI_, 2);                    \
-    else if (ni <= 3) LNS(TI_, 3);               \
-    else if (ni <= 4) LNS(TI_, 4);               \
-    else if (ni <= 6) LNS(TI_, 6);               \
-    else if (ni <= 8) LNS(TI_, 8);               \
-    else if (ni <= 12) LNS(TI_, 12);             \
-    else LNS(TI_, 16);                           \
-  } while (0)
+  auto scalar = [&](auto io) {  // io: a value of the element type, uint16_t (bf16) or float
+    using T = decltype(io);
+    mmr::pick_ceil<2, 3, 4, 6, 8, 12, 16>(ni, [&](auto n) {
+      ln_rows<T, T, decltype(n)::value><<<grid, 256, 0, st>>>((const T*)x, ldx, alpha, (const T*)residual, ldr, gamma, beta,
+                                                             post, ldp, post_scale, (T*)y, ldy, rows, c, eps, groups,
+                                                             group_div);
+    });
+  };
   if (io_bf16)
-    LNS_DISPATCH(uint16_t);
+    scalar(uint16_t{});
   else {
     auto al = [](const void* p, int64_t ld, int vw) {
       return p == nullptr || (((uintptr_t)p & (4 * vw - 1)) == 0 && ld % vw == 0);
@@ -942,23 +927,23 @@ mmr_status mmr_ln_rows(const void* x, int64_t ldx, const float* alpha, const voi
       return c % (64 * vw) == 0 && al(x, ldx, vw) && al(residual, ldr, vw) && al(post, ldp, vw) && al(y, ldy, vw) &&
              al(gamma, 0, vw) && al(beta, 0, vw);
     };
-#define LNV(VW_)                                                                                                  \
-  ln_rows_v<VW_><<<grid, 256, 0, st>>>((const float*)x, ldx, alpha, (const float*)residual, ldr, gamma, beta, post, \
-                                       ldp, post_scale, (float*)y, ldy, rows, c, eps, groups, group_div)
-#define LNSM(LPR_, PER_)                                                                                          \
-  ln_rows_s<LPR_, PER_><<<dim3((unsigned)mmr::ceil_div(rows, 4 * (64 / LPR_))), 256, 0, st>>>(                  \
-      (const float*)x, ldx, alpha, (const float*)residual, ldr, gamma, beta, post, ldp, post_scale, (float*)y, ldy, \
-      rows, c, eps, groups, group_div)
-    if (ok(4)) LNV(4);
-    else if (ok(2)) LNV(2);
-    else if (c <= 128) LNSM(16, 8);
-    else if (c <= 256) LNSM(32, 8);
-    else LNS_DISPATCH(float);
-#undef LNSM
-#undef LNV
+    const float* xf = (const float*)x;
+    const float* rf = (const float*)residual;
+    float* yf = (float*)y;
+    const int vecw = ok(4) ? 4 : (ok(2) ? 2 : 0);
+    if (vecw)  // rows as 16-B / 8-B vectors
+      mmr::pick<4, 2>(vecw, [&](auto vw) {
+        ln_rows_v<vw()><<<grid, 256, 0, st>>>(xf, ldx, alpha, rf, ldr, gamma, beta, post, ldp, post_scale, yf, ldy, rows, c,
+                                              eps, groups, group_div);
+      });
+    else if (c <= 256)  // 16 / 32 lanes per row
+      mmr::pick<16, 32>(c <= 128 ? 16 : 32, [&](auto lpr) {
+        ln_rows_s<lpr(), 8><<<dim3((unsigned)mmr::ceil_div(rows, 4 * (64 / lpr()))), 256, 0, st>>>(
+            xf, ldx, alpha, rf, ldr, gamma, beta, post, ldp, post_scale, yf, ldy, rows, c, eps, groups, group_div);
+      });
+    else
+      scalar(float{});
   }
-#undef LNS_DISPATCH
-#undef LNS
   MMR_LAUNCH_CHECK();
   return MMR_OK;
 }
@@ -977,19 +962,9 @@ mmr_status mmr_ln_rows_split(const float* x, int64_t ldx, const float* alpha, co
   const int nch = (c + 127) / 128;
   const dim3 grid((unsigned)mmr::ceil_div(rows, 8));
   hipStream_t st = mmr::as_stream(stream);
-#define LNSP(N_) \
-  ln_rows_split<N_><<<grid, 256, 0, st>>>(x, ldx, alpha, residual, ldr, gamma, beta, y, ldy, xs, rows, c, eps)
-  switch (nch) {
-    case 1: LNSP(1); break;
-    case 2: LNSP(2); break;
-    case 3: LNSP(3); break;
-    case 4: LNSP(4); break;
-    case 5: LNSP(5); break;
-    case 6: LNSP(6); break;
-    case 7: LNSP(7); break;
-    default: LNSP(8); break;
-  }
-#undef LNSP
+  mmr::pick_ceil<1, 2, 3, 4, 5, 6, 7, 8>(nch, [&](auto n) {
+    ln_rows_split<n()><<<grid, 256, 0, st>>>(x, ldx, alpha, residual, ldr, gamma, beta, y, ldy, xs, rows, c, eps);
+  });
   MMR_LAUNCH_CHECK();
   return MMR_OK;
 }

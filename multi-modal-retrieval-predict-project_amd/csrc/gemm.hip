@@ -1764,6 +1764,50 @@ __global__ __launch_bounds__(256) void quantize_mxfp8(const uint16_t* __restrict
   }
 }
 
+// The 8-phase GEMM's arguments by name (host side; the kernel keeps its positional signature).  A launch
+// site sets the groups its form of the kernel reads and leaves the rest at their defaults.
+struct P8Args {
+  // operands and shape: M a multiple of 256, N of the tile width 64 NT (FP8: byte matrices, K in bytes)
+  const uint16_t* x = nullptr;
+  const uint16_t* w = nullptr;
+  const float* bias = nullptr;
+  const uint16_t* r = nullptr;
+  uint16_t* y = nullptr;
+  int64_t m = 0;
+  int n = 0, k = 0;
+  // FP8 / OUT8: the MX-fp8 scale images of X and W, and of the output
+  const uint8_t* xs = nullptr;
+  const uint8_t* ws = nullptr;
+  uint8_t* ys = nullptr;
+  // KNN: unit and block maxima with their row strides, the valid gallery rows, inverse row norms
+  float* gm = nullptr;
+  float* bm = nullptr;
+  int64_t ldg = 0, ldb = 0, nval = 0;
+  const float* rs = nullptr;
+  int ntst = 0;  // non-temporal output stores (p8_nt)
+  // LNM / STO: row coefficients, the fold's column vectors, row statistics out
+  const float* lc = nullptr;
+  const float* v1 = nullptr;
+  const float* v2 = nullptr;
+  float* sp = nullptr;
+  int ldn = 0;  // OF32: the output's row width (N is padded to the tile width)
+};
+
+// The one launch of gemm_bf16_tn_p8: persistent grid of a multiple of 8 workgroups (one per CU, tiles split
+// evenly per XCD), at most the tile count rounded down to 8 and at least 8.
+template <int NT, int ACT, bool HB, bool HR, bool FP8 = false, bool OUT8 = false, int KNN = 0, int LNM = 0,
+          bool STO = false, bool OF32 = false, bool OSPL = false, bool X3P = false>
+void launch_p8(const P8Args& a, hipStream_t st) {
+  constexpr int NV = LNM == 2 ? 3 : (LNM == 1 ? 2 : 1);
+  const int tm = (int)(a.m / 256), tn = a.n / (64 * NT);
+  const int64_t cus = std::max(8, cu_count() / 8 * 8);
+  const int64_t grid = std::max<int64_t>(8, std::min<int64_t>(cus, (int64_t)tm * tn) / 8 * 8);
+  gemm_bf16_tn_p8<NT, ACT, HB, HR, FP8, OUT8, KNN, LNM, STO, OF32, OSPL, X3P>
+      <<<dim3((unsigned)grid), dim3(512), P8<NT, FP8, 0, NV>::LDS_B, st>>>(
+          a.x, a.w, a.bias, a.r, a.y, a.m, a.n, a.k, tm, tn, a.xs, a.ws, a.ys, a.gm, a.bm, a.ldg, a.ldb, a.nval,
+          a.ntst, a.rs, a.lc, a.v1, a.v2, a.sp, a.ldn);
+}
+
 // Kernel variants: (w4, cfg) pairs the launcher understands.  w4: 0 no persistent kernel, 1 the
 // 4-wave persistent kernel (256x256 or 256x192 tiles), 2 persistent 256x192 only; cfg: the 8-wave
 // tile when w4 does not apply (0 off -> 128x128; 1 256x256 KB64 x2; 2 256x256 KB32 x4;
@@ -1797,19 +1841,11 @@ void launch(const uint16_t* x, const uint16_t* w, const float* b, const uint16_t
     }
   }
   if (cfg >= 7 && k % 128 == 0 && m % 256 == 0) {  // persistent 8-phase: 7 -> 256x256, 8 -> 256x192
-    const int grid = std::max(8, cu_count() / 8 * 8);
-    if (cfg == 7 && n % 256 == 0) {
-      const int tm = (int)t256, tn = n / 256;
-      gemm_bf16_tn_p8<4, ACT, HB, HR><<<dim3(std::max<int64_t>(8, std::min<int64_t>(grid, (int64_t)tm * tn) / 8 * 8)), dim3(512), P8<4>::LDS_B, st>>>(
-          x, w, b, r, y, m, n, k, tm, tn, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, 0, p8_nt(m, n, 2));
-      return;
-    }
-    if (cfg == 8 && n % 192 == 0) {
-      const int tm = (int)t256, tn = n / 192;
-      gemm_bf16_tn_p8<3, ACT, HB, HR><<<dim3(std::max<int64_t>(8, std::min<int64_t>(grid, (int64_t)tm * tn) / 8 * 8)), dim3(512), P8<3>::LDS_B, st>>>(
-          x, w, b, r, y, m, n, k, tm, tn, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, 0, p8_nt(m, n, 2));
-      return;
-    }
+    P8Args a;
+    a.x = x, a.w = w, a.bias = b, a.r = r, a.y = y, a.m = m, a.n = n, a.k = k;
+    a.ntst = p8_nt(m, n, 2);
+    if (cfg == 7 && n % 256 == 0) return launch_p8<4, ACT, HB, HR>(a, st);
+    if (cfg == 8 && n % 192 == 0) return launch_p8<3, ACT, HB, HR>(a, st);
   }
   if (cfg != 0 && k >= 256 && m >= 4096) {
     if (cfg <= 2 && n % 256 == 0 && t256 * (n / 256) >= 512) {
@@ -1952,17 +1988,8 @@ extern "C" mmr_status mmr_linear_bf16(const uint16_t* x, const uint16_t* w, cons
   hipStream_t st = mmr::as_stream(stream);
   const bool hb = bias != nullptr, hr = residual != nullptr;
   auto run = [&](int w4, int cfg) {
-    if (act == 0) {
-      if (hb && hr) launch<0, true, true>(x, w, bias, residual, y, m, n, k, st, w4, cfg);
-      else if (hb) launch<0, true, false>(x, w, bias, residual, y, m, n, k, st, w4, cfg);
-      else if (hr) launch<0, false, true>(x, w, bias, residual, y, m, n, k, st, w4, cfg);
-      else launch<0, false, false>(x, w, bias, residual, y, m, n, k, st, w4, cfg);
-    } else {
-      if (hb && hr) launch<1, true, true>(x, w, bias, residual, y, m, n, k, st, w4, cfg);
-      else if (hb) launch<1, true, false>(x, w, bias, residual, y, m, n, k, st, w4, cfg);
-      else if (hr) launch<1, false, true>(x, w, bias, residual, y, m, n, k, st, w4, cfg);
-      else launch<1, false, false>(x, w, bias, residual, y, m, n, k, st, w4, cfg);
-    }
+    mmr::pick_flags([&](auto a, auto b, auto r) { launch<a(), b(), r()>(x, w, bias, residual, y, m, n, k, st, w4, cfg); },
+                    act != 0, hb, hr);
   };
   // the pinned variant (mmr_pin_variant), else the shape's tuned variant (tuned once per process on
   // the first call with that shape)
@@ -1990,13 +2017,11 @@ int ln_nt(int64_t m, int n) {
 template <int NT, int ACT, bool HR, int LNM, bool STO>
 void launch_ln(const uint16_t* x, const uint16_t* w, const float* b, const uint16_t* r, uint16_t* y, int64_t m,
                int n, int k, const float* lc, const float* v1, const float* v2, float* sp, hipStream_t st) {
-  constexpr int NV = LNM == 2 ? 3 : (LNM == 1 ? 2 : 1);
-  const int grid = std::max(8, cu_count() / 8 * 8);
-  const int tm = (int)(m / 256), tn = n / (64 * NT);
-  gemm_bf16_tn_p8<NT, ACT, true, HR, false, false, 0, LNM, STO>
-      <<<dim3(std::max<int64_t>(8, std::min<int64_t>(grid, (int64_t)tm * tn) / 8 * 8)), dim3(512),
-         P8<NT, false, 0, NV>::LDS_B, st>>>(x, w, b, r, y, m, n, k, tm, tn, nullptr, nullptr, nullptr, nullptr,
-                                            nullptr, 0, 0, 0, p8_nt(m, n, 2), nullptr, lc, v1, v2, sp);
+  P8Args a;
+  a.x = x, a.w = w, a.bias = b, a.r = r, a.y = y, a.m = m, a.n = n, a.k = k;
+  a.ntst = p8_nt(m, n, 2);
+  a.lc = lc, a.v1 = v1, a.v2 = v2, a.sp = sp;
+  launch_p8<NT, ACT, true, HR, false, false, 0, LNM, STO>(a, st);
 }
 
 // ---- fp32-faithful (x3) linears on the 8-phase GEMM: Y = X W^T + b with f32 accumulation over the split
@@ -2035,12 +2060,10 @@ __global__ __launch_bounds__(256) void x3_split_rows(const float* __restrict__ x
 template <int NT, int ACT, bool HB, bool HR, bool OSPL = false>
 void launch_x3p8(const uint16_t* xs, const uint16_t* w2, const float* b, const float* r, void* y, int64_t m, int npad,
                  int n, int kp, hipStream_t st) {
-  const int grid = std::max(8, cu_count() / 8 * 8);
-  const int tm = (int)(m / 256), tn = npad / (64 * NT);
-  gemm_bf16_tn_p8<NT, ACT, HB, HR, false, false, 0, 0, false, true, OSPL, true>
-      <<<dim3(std::max<int64_t>(8, std::min<int64_t>(grid, (int64_t)tm * tn) / 8 * 8)), dim3(512), P8<NT>::LDS_B, st>>>(
-          xs, w2, b, (const uint16_t*)r, (uint16_t*)y, m, npad, 2 * kp, tm, tn, nullptr, nullptr, nullptr, nullptr,
-          nullptr, 0, 0, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, n);
+  P8Args a;
+  a.x = xs, a.w = w2, a.bias = b, a.r = (const uint16_t*)r, a.y = (uint16_t*)y, a.m = m, a.n = npad, a.k = 2 * kp;
+  a.ldn = n;
+  launch_p8<NT, ACT, HB, HR, false, false, 0, 0, false, true, OSPL, true>(a, st);
 }
 }  // namespace
 
@@ -2142,35 +2165,17 @@ extern "C" mmr_status mmr_x3_linear_p8(const uint16_t* xs, const uint16_t* w2, c
   hipStream_t st = mmr::as_stream(stream);
   const int nt = out_hilo ? 3 : (npad % 192 == 0 && npad % 256 == 0 ? ln_nt(m, npad) : (npad % 256 == 0 ? 4 : 3));
   const bool hb = bias != nullptr, hr = residual != nullptr;
-  if (out_hilo) {
-    if (act) {
-      if (hb) launch_x3p8<3, 1, true, false, true>(xs, w2, bias, nullptr, y, m, npad, n, kp, st);
-      else launch_x3p8<3, 1, false, false, true>(xs, w2, bias, nullptr, y, m, npad, n, kp, st);
-    } else {
-      if (hb) launch_x3p8<3, 0, true, false, true>(xs, w2, bias, nullptr, y, m, npad, n, kp, st);
-      else launch_x3p8<3, 0, false, false, true>(xs, w2, bias, nullptr, y, m, npad, n, kp, st);
-    }
-    MMR_LAUNCH_CHECK();
-    return MMR_OK;
-  }
-  void* yf = y;
-#define X3P8(NT_)                                                                                       \
-  do {                                                                                                   \
-    if (act) {                                                                                           \
-      if (hb && hr) launch_x3p8<NT_, 1, true, true>(xs, w2, bias, residual, yf, m, npad, n, kp, st);   \
-      else if (hb) launch_x3p8<NT_, 1, true, false>(xs, w2, bias, residual, yf, m, npad, n, kp, st);   \
-      else if (hr) launch_x3p8<NT_, 1, false, true>(xs, w2, bias, residual, yf, m, npad, n, kp, st);   \
-      else launch_x3p8<NT_, 1, false, false>(xs, w2, bias, residual, yf, m, npad, n, kp, st);          \
-    } else {                                                                                             \
-      if (hb && hr) launch_x3p8<NT_, 0, true, true>(xs, w2, bias, residual, yf, m, npad, n, kp, st);   \
-      else if (hb) launch_x3p8<NT_, 0, true, false>(xs, w2, bias, residual, yf, m, npad, n, kp, st);   \
-      else if (hr) launch_x3p8<NT_, 0, false, true>(xs, w2, bias, residual, yf, m, npad, n, kp, st);   \
-      else launch_x3p8<NT_, 0, false, false>(xs, w2, bias, residual, yf, m, npad, n, kp, st);          \
-    }                                                                                                    \
-  } while (0)
-  if (nt == 4) X3P8(4);
-  else X3P8(3);
-#undef X3P8
+  if (out_hilo)  // split output: 256 x 192 tiles, no residual
+    mmr::pick_flags([&](auto a, auto b) { launch_x3p8<3, a(), b(), false, true>(xs, w2, bias, nullptr, y, m, npad, n, kp, st); },
+                    act != 0, hb);
+  else
+    mmr::pick<3, 4>(nt, [&](auto t) {
+      mmr::pick_flags(
+          [&](auto a, auto b, auto r) {
+            launch_x3p8<decltype(t)::value, a(), b(), r()>(xs, w2, bias, residual, y, m, npad, n, kp, st);
+          },
+          act != 0, hb, hr);
+    });
   MMR_LAUNCH_CHECK();
   return MMR_OK;
 }
@@ -2195,28 +2200,30 @@ extern "C" mmr_status mmr_linear_bf16_ln(const uint16_t* x, const uint16_t* w, c
   const bool hr = residual != nullptr, so = stats_out != nullptr;
   // the combinations the BERT layer uses (towers.py): QKV / FFN1 (fold, + GELU for FFN1), O-proj /
   // FFN2 (normalised or plain residual, row statistics out)
-#define LN_L(NT_, A_, HR_, M_, S_)                                                                              \
-  launch_ln<NT_, A_, HR_, M_, S_>(x, w, bias, residual, y, m, n, k, ln_coef, ln_v1, ln_v2, stats_out, st)
-#define LN_NT(A_, HR_, M_, S_) (nt == 3 ? LN_L(3, A_, HR_, M_, S_) : LN_L(4, A_, HR_, M_, S_))
+  auto ln = [&](auto t, auto a, auto r, auto lm, auto s) {  // (NT, ACT, HR, LNM, STO)
+    launch_ln<decltype(t)::value, decltype(a)::value, decltype(r)::value, decltype(lm)::value, decltype(s)::value>(
+        x, w, bias, residual, y, m, n, k, ln_coef, ln_v1, ln_v2, stats_out, st);
+  };
+  using I0 = std::integral_constant<int, 0>;
+  using I1 = std::integral_constant<int, 1>;
+  using I2 = std::integral_constant<int, 2>;
+  using I3 = std::integral_constant<int, 3>;
   if (ln_mode == 1 && !hr && !so) {
-    if (act) LN_NT(1, false, 1, false);
-    else LN_NT(0, false, 1, false);
+    mmr::pick<3, 4>(nt, [&](auto t) {
+      mmr::pick<0, 1>(act, [&](auto a) { ln(t, a, std::false_type{}, I1{}, std::false_type{}); });
+    });
   } else if (ln_mode == 2 && act == 0) {
     // 256 x 192 tiles only: the 256 x 256 form of the normalised residual exceeds 256 VGPRs (a spill
     // in this kernel would also skew the K loop's counted vmcnt waits)
     MMR_REQUIRE(n % 192 == 0, "mmr_linear_bf16_ln: ln_mode 2 needs n %% 192 == 0 (n=%d)", n);
-    if (so) LN_L(3, 0, true, 2, true);
-    else LN_L(3, 0, true, 2, false);
+    mmr::pick_flags([&](auto s) { ln(I3{}, I0{}, std::true_type{}, I2{}, s); }, so);
   } else if (ln_mode == 0 && act == 0 && so) {
-    if (hr) LN_NT(0, true, 0, true);
-    else LN_NT(0, false, 0, true);
+    mmr::pick<3, 4>(nt, [&](auto t) { mmr::pick_flags([&](auto r) { ln(t, I0{}, r, I0{}, std::true_type{}); }, hr); });
   } else {
     mmr::set_error("mmr_linear_bf16_ln: ln_mode=%d act=%d residual=%d stats_out=%d not built", ln_mode, act, (int)hr,
                    (int)so);
     return MMR_ERR_UNSUPPORTED;
   }
-#undef LN_NT
-#undef LN_L
   MMR_LAUNCH_CHECK();
   return MMR_OK;
 }
@@ -2251,33 +2258,14 @@ extern "C" mmr_status mmr_linear_mxfp8(const uint8_t* xq, const uint8_t* xs, con
   MMR_REQUIRE(kp > 0 && kp % 256 == 0, "mmr_linear_mxfp8: kp=%d must be a positive multiple of 256", kp);
   MMR_REQUIRE(act == 0 || act == 1, "mmr_linear_mxfp8: act=%d", act);
   hipStream_t st = mmr::as_stream(stream);
-  const int tm = (int)(m / 256), tn = n / tbn;
-  const int grid = (int)std::max<int64_t>(8, std::min<int64_t>(std::max(8, cu_count() / 8 * 8), (int64_t)tm * tn) / 8 * 8);
-  const bool hb = bias != nullptr, hr = residual != nullptr;
-  const uint16_t* X = (const uint16_t*)xq;
-  const uint16_t* W = (const uint16_t*)wq;
-  const int nts = p8_nt(m, n, 2);
-#define MX_LAUNCH(A, B, R)                                                                                         \
-  do {                                                                                                               \
-    if (w_layout == 1)                                                                                               \
-      gemm_bf16_tn_p8<3, A, B, R, true><<<dim3(grid), dim3(512), P8<3, true>::LDS_B, st>>>(X, W, bias, residual, y, m, \
-                                                                                          n, kp, tm, tn, xs, ws, nullptr, nullptr, nullptr, 0, 0, 0, nts); \
-    else                                                                                                             \
-      gemm_bf16_tn_p8<4, A, B, R, true><<<dim3(grid), dim3(512), P8<4, true>::LDS_B, st>>>(X, W, bias, residual, y, m, \
-                                                                                          n, kp, tm, tn, xs, ws, nullptr, nullptr, nullptr, 0, 0, 0, nts); \
-  } while (0)
-  if (act == 0) {
-    if (hb && hr) MX_LAUNCH(0, true, true);
-    else if (hb) MX_LAUNCH(0, true, false);
-    else if (hr) MX_LAUNCH(0, false, true);
-    else MX_LAUNCH(0, false, false);
-  } else {
-    if (hb && hr) MX_LAUNCH(1, true, true);
-    else if (hb) MX_LAUNCH(1, true, false);
-    else if (hr) MX_LAUNCH(1, false, true);
-    else MX_LAUNCH(1, false, false);
-  }
-#undef MX_LAUNCH
+  P8Args a;
+  a.x = (const uint16_t*)xq, a.w = (const uint16_t*)wq, a.bias = bias, a.r = residual, a.y = y, a.m = m, a.n = n, a.k = kp;
+  a.xs = xs, a.ws = ws;
+  a.ntst = p8_nt(m, n, 2);
+  mmr::pick<3, 4>(tbn / 64, [&](auto t) {
+    mmr::pick_flags([&](auto ac, auto hb, auto hr) { launch_p8<decltype(t)::value, ac(), hb(), hr(), true>(a, st); },
+                    act != 0, bias != nullptr, residual != nullptr);
+  });
   MMR_LAUNCH_CHECK();
   return MMR_OK;
 }
@@ -2292,19 +2280,11 @@ extern "C" mmr_status mmr_linear_mxfp8_q8(const uint8_t* xq, const uint8_t* xs, 
   MMR_REQUIRE(kp > 0 && kp % 256 == 0, "mmr_linear_mxfp8_q8: kp=%d must be a positive multiple of 256", kp);
   MMR_REQUIRE(act == 0 || act == 1, "mmr_linear_mxfp8_q8: act=%d", act);
   hipStream_t st = mmr::as_stream(stream);
-  const int tm = (int)(m / 256), tn = n / 256;
-  const int grid = (int)std::max<int64_t>(8, std::min<int64_t>(std::max(8, cu_count() / 8 * 8), (int64_t)tm * tn) / 8 * 8);
-  const uint16_t* X = (const uint16_t*)xq;
-  const uint16_t* W = (const uint16_t*)wq;
-  uint16_t* Y = (uint16_t*)yq;
-  if (act == 0 && bias)
-    gemm_bf16_tn_p8<4, 0, true, false, true, true><<<dim3(grid), dim3(512), P8<4, true>::LDS_B, st>>>(X, W, bias, nullptr, Y, m, n, kp, tm, tn, xs, ws, ys, nullptr, nullptr, 0, 0, 0, p8_nt(m, n, 1));
-  else if (act == 0)
-    gemm_bf16_tn_p8<4, 0, false, false, true, true><<<dim3(grid), dim3(512), P8<4, true>::LDS_B, st>>>(X, W, bias, nullptr, Y, m, n, kp, tm, tn, xs, ws, ys, nullptr, nullptr, 0, 0, 0, p8_nt(m, n, 1));
-  else if (bias)
-    gemm_bf16_tn_p8<4, 1, true, false, true, true><<<dim3(grid), dim3(512), P8<4, true>::LDS_B, st>>>(X, W, bias, nullptr, Y, m, n, kp, tm, tn, xs, ws, ys, nullptr, nullptr, 0, 0, 0, p8_nt(m, n, 1));
-  else
-    gemm_bf16_tn_p8<4, 1, false, false, true, true><<<dim3(grid), dim3(512), P8<4, true>::LDS_B, st>>>(X, W, bias, nullptr, Y, m, n, kp, tm, tn, xs, ws, ys, nullptr, nullptr, 0, 0, 0, p8_nt(m, n, 1));
+  P8Args a;
+  a.x = (const uint16_t*)xq, a.w = (const uint16_t*)wq, a.bias = bias, a.y = (uint16_t*)yq, a.m = m, a.n = n, a.k = kp;
+  a.xs = xs, a.ws = ws, a.ys = ys;
+  a.ntst = p8_nt(m, n, 1);
+  mmr::pick_flags([&](auto ac, auto hb) { launch_p8<4, ac(), hb(), false, true, true>(a, st); }, act != 0, bias != nullptr);
   MMR_LAUNCH_CHECK();
   return MMR_OK;
 }
@@ -2319,15 +2299,11 @@ namespace mmr {
 hipError_t knn_scan_p8(const uint16_t* qh, const uint16_t* gh, int K, int tiles_n, int64_t nval, float* gm,
                        int64_t ldG, float* bm, int64_t ldB, int unit_rows, hipStream_t st, int tiles_m,
                        const float* rs) {
-  const int grid = std::max(8, std::min(cu_count(), tiles_m * tiles_n) / 8 * 8);
-  if (unit_rows == 2)
-    gemm_bf16_tn_p8<4, 0, false, false, false, false, 2><<<dim3(grid), dim3(512), P8<4>::LDS_B, st>>>(
-        qh, gh, nullptr, nullptr, nullptr, 256 * tiles_m, tiles_n * 256, K, tiles_m, tiles_n, nullptr, nullptr, nullptr,
-        gm, bm, ldG, ldB, nval, 0, rs);
-  else
-    gemm_bf16_tn_p8<4, 0, false, false, false, false, 4><<<dim3(grid), dim3(512), P8<4>::LDS_B, st>>>(
-        qh, gh, nullptr, nullptr, nullptr, 256 * tiles_m, tiles_n * 256, K, tiles_m, tiles_n, nullptr, nullptr, nullptr,
-        gm, bm, ldG, ldB, nval, 0, rs);
+  P8Args a;
+  a.x = qh, a.w = gh, a.m = 256 * tiles_m, a.n = tiles_n * 256, a.k = K;
+  a.gm = gm, a.bm = bm, a.ldg = ldG, a.ldb = ldB, a.nval = nval, a.rs = rs;
+  if (unit_rows == 2) launch_p8<4, 0, false, false, false, false, 2>(a, st);
+  else launch_p8<4, 0, false, false, false, false, 4>(a, st);
   return hipGetLastError();
 }
 }  // namespace mmr

@@ -205,17 +205,11 @@ extern "C" mmr_status mmr_linear_rw(const uint16_t* x, const uint16_t* img, cons
   MMR_REQUIRE(parts > 0 && m >= 0, "mmr_linear_rw: M=%lld N=%d K=%d not supported", (long long)m, n, k);
   if (m == 0) return MMR_OK;
   hipStream_t st = mmr::as_stream(stream);
-  const bool hb = bias != nullptr, hr = residual != nullptr;
-#define RW_K(KK)                                                                         \
-  if (k == KK) {                                                                         \
-    if (hb && hr) launch_rw<KK, true, true>(x, img, bias, residual, y, m, n, parts, st);   \
-    else if (hb) launch_rw<KK, true, false>(x, img, bias, residual, y, m, n, parts, st);   \
-    else if (hr) launch_rw<KK, false, true>(x, img, bias, residual, y, m, n, parts, st);   \
-    else launch_rw<KK, false, false>(x, img, bias, residual, y, m, n, parts, st);          \
-  }
-  RW_K(64)
-  else RW_K(192)
-#undef RW_K
+  mmr::pick<64, 192>(k, [&](auto kk) {
+    mmr::pick_flags(
+        [&](auto hb, auto hr) { launch_rw<decltype(kk)::value, hb(), hr()>(x, img, bias, residual, y, m, n, parts, st); },
+        bias != nullptr, residual != nullptr);
+  });
   MMR_LAUNCH_CHECK();
   return MMR_OK;
 }

@@ -59,6 +59,7 @@ using mmr::f16x8;
 using mmr::f32x16;
 using mmr::f32x4;
 using mmr::LGKM0;
+using mmr::pick;
 using mmr::round_up;
 using mmr::u32x4;
 using mmr::vmcnt_n;
@@ -2227,38 +2228,214 @@ constexpr int64_t kSkinnyMaxQ = 32;
 // query tiles per p8 pass with 4-row units (2 / 4 measured: 4, profiles/r03_s4_knn_pair_ab.txt)
 constexpr int kP8PairTiles = 4;
 
-template <int WQ, int MQ, int WR, int MR, bool PF>
-void launch_f16_tile(hipStream_t st, const mmr_index* ix, const uint16_t* qh, float* gm, float* bm, int64_t ldG,
-                     int64_t ldB, int64_t n_rt) {
-  using C = F16TileCfg<WQ, MQ, WR, MR, PF>;
-  const size_t lds = (size_t)C::STAGES * C::SLICE_B;
-  knn_scan_f16_tile<WQ, MQ, WR, MR, PF><<<dim3((unsigned)ix->n_cu), dim3(64 * C::NW), lds, st>>>(
-      qh, ix->gh, gm, bm, ix->Dp, ldG, ldB, ix->n, n_rt, scan_rscale(ix));
-}
+// A search's outputs ([nq][k] each; all but idx optional, status [nq]) and K; at(q0): the rows from query q0 on
+struct SearchOut {
+  int64_t* idx;
+  float* score;
+  double* score64;
+  int32_t* status;
+  int k;
+  SearchOut at(int64_t q0) const {
+    return {idx + q0 * k, score ? score + q0 * k : nullptr, score64 ? score64 + q0 * k : nullptr,
+            status ? status + q0 : nullptr, k};
+  }
+};
 
 // COARSE selections (block maxima first) run 512-thread workgroups, the unit-level ones 1024
 template <int MODE, bool COARSE = false, bool RAW = false>
 void launch_select(hipStream_t st, int64_t nq, const float* vals, int64_t ldV, int64_t nunits, const mmr_index* ix,
-                   int k, float two_delta, const float* q_raw, const double* qnorm64, int64_t* oi, float* os,
-                   double* os64, int32_t* ost, const float* bvals = nullptr, int64_t ldB = 0,
-                   float two_delta_abs = 0.f, const double* qpre = nullptr) {
+                   float two_delta, const float* q_raw, const double* qnorm64, const SearchOut& o,
+                   const float* bvals = nullptr, int64_t ldB = 0, float two_delta_abs = 0.f,
+                   const double* qpre = nullptr) {
   constexpr int T = COARSE ? 512 : kSelThreads;
   const dim3 g((unsigned)nq), b(T);
-#define MMR_SEL(NC)                                                                                              \
-  knn_select_t<MODE, NC, T, COARSE, RAW><<<g, b, 0, st>>>(vals, ldV, nunits, ix->n, k, two_delta, bvals, ldB,    \
-                                                          two_delta_abs, q_raw, ix->d, qnorm64, ix->gal, ix->Dp,  \
-                                                          ix->norm64, ix->idx_base,                               \
-                                                          ix->dtype == MMR_F16 ? ix->gh : nullptr, oi, os, os64,  \
-                                                          ost, qpre)
   // NC = 256-float chunks of a row in the f64 re-score (0: d > 1024, strided loop)
-  switch (ix->d > 1024 ? 0 : (int)ceil_div(ix->Dp, 256)) {
-    case 1: MMR_SEL(1); break;
-    case 2: MMR_SEL(2); break;
-    case 3: MMR_SEL(3); break;
-    case 4: MMR_SEL(4); break;
-    default: MMR_SEL(0); break;
-  }
-#undef MMR_SEL
+  pick<0, 1, 2, 3, 4>(ix->d > 1024 ? 0 : (int)ceil_div(ix->Dp, 256), [&](auto nc) {
+    knn_select_t<MODE, nc(), T, COARSE, RAW><<<g, b, 0, st>>>(
+        vals, ldV, nunits, ix->n, o.k, two_delta, bvals, ldB, two_delta_abs, q_raw, ix->d, qnorm64, ix->gal, ix->Dp,
+        ix->norm64, ix->idx_base, ix->dtype == MMR_F16 ? ix->gh : nullptr, o.idx, o.score, o.score64, o.status, qpre);
+  });
+}
+
+// Threshold margins 2 delta of the scans, |s_approx - s64| <= delta:
+//  f32 (knn_scores, knn_scan_f32_gmax): (Dp + 16) 2^-24 — f32 products accumulated in f32 over Dp
+//      terms of a unit query against g/|g| (|sum| <= 1), plus the normalisations;
+//  x3: + the dropped lo*lo bf16 terms and the bf16 rounding of the split, (3Dp + 16) 2^-24 + 4 2^-16;
+//  f16: fp16 rounding of both unit vectors, 2 * 2^-11 relative with sum |q_k g_k| <= 1
+//      (Cauchy-Schwarz) -> 2^-10; fp16 subnormal half-ulps (components below 2^-14 are held to
+//      2^-25 absolute): sum_k (|q_k| + |g_k|) 2^-25 <= 2 sqrt(Dp) 2^-25 (Cauchy-Schwarz again),
+//      computed from Dp below; f32 accumulation (Dp terms) and the f32 normalisation of both
+//      operands (the f32-mode bound, doubled: (2Dp + 64) 2^-24).
+//  f16 RAW (knn_scan_f16_gmax<RAW>: fp16(q) . g^ for the unnormalised q): the same terms scaled by |q|
+//      — fp16 rounding 2^-10 |q| (Cauchy-Schwarz over |q| |g^|), g^'s subnormal half-ulps
+//      sum |q_k| 2^-25 <= sqrt(Dp) |q| 2^-25, f32 accumulation (2Dp + 64) 2^-24 |q| — plus q's own
+//      subnormal half-ulps sum |g^_k| 2^-25 <= sqrt(Dp) 2^-25, independent of |q|:
+//      delta = |q| f16r / 2 + f16a / 2 (the selection computes |q| first).
+struct Margins {
+  float f32, x3, f16, f16r, f16a;
+};
+Margins margins(int Dp) {
+  const float sq = sqrtf((float)Dp), u24 = 5.9604645e-8f, u25 = 2.9802322e-8f;  // 2^-24, 2^-25
+  Margins m;
+  m.f32 = 2.0f * (float)(Dp + 16) * u24;
+  m.x3 = 2.0f * ((float)(3 * Dp + 16) * u24 + 4.0f * 1.5258789e-5f);
+  m.f16 = 2.0f * (9.765625e-4f + 2.0f * sq * u25 + (float)(2 * Dp + 64) * u24);
+  m.f16r = 2.0f * (9.765625e-4f + sq * u25 + (float)(2 * Dp + 64) * u24);
+  m.f16a = 2.0f * sq * u25;
+  return m;
+}
+
+// (QT, KC) of the one-wave and raw-query fp16 scans: QT tiles of 16 queries; KC = 128 where the rows are whole
+// 128-element chunks, else 64.  WIDE2: the <2, 128> form is built (the prepped one-wave scan only).
+template <bool WIDE2, class F>
+void pick_qt_kc(int qt, int Dp, F&& f) {
+  pick<1, 2>(qt, [&](auto t) {
+    if constexpr (decltype(t)::value == 2 && !WIDE2) f(t, std::integral_constant<int, 64>{});
+    else pick<64, 128>(Dp % 128 == 0 ? 128 : 64, [&](auto kc) { f(t, kc); });
+  });
+}
+
+// the one-wave fp16 stream over 64-row blocks: prepped fp16 unit queries qh, or (RAW) the caller's f32 rows
+template <bool RAW>
+void launch_f16_gmax(hipStream_t st, const mmr_index* ix, const uint16_t* qh, const float* q_raw, int64_t nq_raw, int qt) {
+  pick_qt_kc<!RAW>(qt, ix->Dp, [&](auto t, auto kc) {
+    knn_scan_f16_gmax<t(), kc(), 1, RAW><<<dim3((unsigned)(ix->Np / 64)), 64, 0, st>>>(
+        qh, q_raw, nq_raw, ix->d, ix->gh, ix->vals, ix->bvals, ix->Dp, ix->Np / 4, ix->Np / 64, ix->n, scan_rscale(ix));
+  });
+}
+
+// ---- the routes of mmr_index_search: pq queries qp -> o, each its prep, its scan and its selection.
+// The fp16 scans (mode 2) read the tile32h fp16 image gh (raw rows of a native fp16 index scaled by 1 / |g|,
+// scan_rscale) and write unit maxima to vals and 64-row block maxima to bvals.
+
+// fp16, 129-1024 queries: the persistent 8-phase GEMM (gemm.hip) with the unit-max epilogue —
+// 256-query M tiles x 256-row gallery tiles, row-major fp16 queries, the tile32h gallery.
+// (It computes all 256 query rows; at 100k x 768 it beats the LDS-ring tile scan from Q ~ 160:
+// Q = 64 / 128 / 192 / 256: 81 / 83 / 86 / 88 us vs 62 / 69 / 96 / 100.)
+mmr_status search_f16_p8(const mmr_index* ix, hipStream_t st, const float* qp, int64_t pq, bool u2, const SearchOut& o,
+                         const Margins& md) {
+  const int tm = (int)((pq + 255) / 256);  // query tiles of this pass
+  knn_prep_queries<<<dim3(64 * tm), dim3(256), 0, st>>>(qp, pq, ix->d, ix->qn, ix->Dp, 256 * tm, ix->qnorm64, 3);
+  MMR_LAUNCH_CHECK();
+  // unit size: 2 rows halves the rows the select re-scores per candidate unit, 4 rows halves
+  // the unit maxima the scan writes (512 vs 256 MB per pass at 1M rows): 2 for small
+  // galleries or large K (cfg2 100k / K 10: select 22 -> 16 us; cfg3 1M / K 50: 104 -> 65 us for
+  // +30 us of scan), 4 for large galleries at small K (cfg5 1M / K 10: +37 us scan, -9 select)
+  const int64_t ldG8 = ix->Np / (u2 ? 2 : 4), ldB8 = ix->Np / 64;
+  MMR_CHECK_HIP(mmr::knn_scan_p8((const uint16_t*)ix->qn, ix->gh, ix->Dp, (int)(ix->Np / 256), ix->n, ix->vals, ldG8,
+                                 ix->bvals, ldB8, u2 ? 2 : 4, st, tm, scan_rscale(ix)));
+  if (u2) launch_select<3, true>(st, pq, ix->vals, ldG8, ldG8, ix, md.f16, qp, ix->qnorm64, o, ix->bvals, ldB8);
+  else launch_select<2, true>(st, pq, ix->vals, ldG8, ldG8, ix, md.f16, qp, ix->qnorm64, o, ix->bvals, ldB8);
+  MMR_LAUNCH_CHECK();
+  return MMR_OK;
+}
+
+// fp16, 33-256 queries: the LDS-staged tile scan (64 / 128 / 256-query tiles), contiguous units
+mmr_status search_f16_tile(const mmr_index* ix, hipStream_t st, const float* qp, int64_t pq, const SearchOut& o,
+                           const Margins& md) {
+  const int wq = pq <= 64 ? 1 : pq <= 128 ? 2 : 4;
+  const int64_t Qt = 64 * wq, ldG = ix->Np / 4, ldB = ix->Np / 64;
+  knn_prep_queries<<<dim3((unsigned)ceil_div(Qt, 4)), dim3(256), 0, st>>>(qp, pq, ix->d, ix->qn, ix->Dp, Qt, ix->qnorm64, 2);
+  MMR_LAUNCH_CHECK();
+  pick<1, 2, 4>(wq, [&](auto w) {  // (WQ, MQ, WR, MR): 4 x 4 waves, 2 x 8 under the 256-query tile
+    constexpr int WQ = decltype(w)::value, WR = WQ == 4 ? 2 : 4, MR = WQ == 4 ? 8 : 4;
+    using C = F16TileCfg<WQ, 4, WR, MR, false>;
+    knn_scan_f16_tile<WQ, 4, WR, MR, false><<<dim3((unsigned)ix->n_cu), dim3(64 * C::NW), (size_t)C::STAGES * C::SLICE_B, st>>>(
+        (const uint16_t*)ix->qn, ix->gh, ix->vals, ix->bvals, ix->Dp, ldG, ldB, ix->n, ix->Np / 16, scan_rscale(ix));
+  });
+  MMR_LAUNCH_CHECK();
+  launch_select<2, true>(st, pq, ix->vals, ldG, ldG, ix, md.f16, qp, ix->qnorm64, o, ix->bvals, ldB);
+  MMR_LAUNCH_CHECK();
+  return MMR_OK;
+}
+
+// fp16, <= 32 queries with 16-B aligned rows (d % 8 == 0): the scan reads the caller's f32 rows itself (no prep
+// launch), per-query margin; rows that fit LDS (Dp <= 1024) take the persistent 8-wave form
+mmr_status search_f16_raw(const mmr_index* ix, hipStream_t st, const float* qp, int64_t pq, const SearchOut& o,
+                          const Margins& md) {
+  const int qt = pq <= 16 ? 1 : 2;
+  const int64_t ldG = ix->Np / 4, ldB = ix->Np / 64;
+  const bool lq = ix->Dp <= 1024;
+  if (lq)
+    pick_qt_kc<false>(qt, ix->Dp, [&](auto t, auto kc) {
+      knn_scan_f16_lq<t(), kc(), 8><<<dim3((unsigned)ix->n_cu), 512, (size_t)t() * 16 * ix->Dp * 2, st>>>(
+          qp, pq, ix->d, ix->gh, ix->vals, ix->bvals, ix->Dp, ldG, ldB, ix->n, ix->Np / 64, ix->qnorm64, scan_rscale(ix));
+    });
+  else
+    launch_f16_gmax<true>(st, ix, nullptr, qp, pq, qt);
+  MMR_LAUNCH_CHECK();
+  launch_select<1, true, true>(st, pq, ix->vals, ldG, ldG, ix, md.f16r, qp, ix->qnorm64, o, ix->bvals, ldB, md.f16a,
+                               lq ? ix->qnorm64 : nullptr);
+  MMR_LAUNCH_CHECK();
+  return MMR_OK;
+}
+
+// fp16, <= 32 queries whose rows are not 16-B aligned / d % 8 != 0: prep + the one-wave stream
+mmr_status search_f16_wave(const mmr_index* ix, hipStream_t st, const float* qp, int64_t pq, const SearchOut& o,
+                           const Margins& md) {
+  const int qt = pq <= 16 ? 1 : 2;
+  const int64_t Qp = 16 * qt, ldG = ix->Np / 4, ldB = ix->Np / 64;
+  knn_prep_queries<<<dim3((unsigned)ceil_div(Qp, 4)), dim3(256), 0, st>>>(qp, pq, ix->d, ix->qn, ix->Dp, Qp, ix->qnorm64, 2);
+  MMR_LAUNCH_CHECK();
+  launch_f16_gmax<false>(st, ix, (const uint16_t*)ix->qn, nullptr, 0, qt);
+  MMR_LAUNCH_CHECK();
+  launch_select<1, true>(st, pq, ix->vals, ldG, ldG, ix, md.f16, qp, ix->qnorm64, o, ix->bvals, ldB);
+  MMR_LAUNCH_CHECK();
+  return MMR_OK;
+}
+
+// x3, <= kSkinnyMaxQ queries: the skinny scan — HBM-streaming f32 MFMA, f32-mode delta
+mmr_status search_x3_skinny(const mmr_index* ix, hipStream_t st, const float* qc, int64_t cq, const SearchOut& o,
+                            const Margins& md) {
+  const int qt = cq <= 16 ? 1 : cq <= 32 ? 2 : 4;
+  const int64_t Qp = 16 * qt, ldG = ix->Np / 4;
+  knn_prep_queries<<<dim3((unsigned)ceil_div(Qp, 4)), dim3(256), 0, st>>>(qc, cq, ix->d, ix->qn, ix->Dp, Qp, ix->qnorm64, 1);
+  MMR_LAUNCH_CHECK();
+  pick<1, 2, 4>(qt, [&](auto t) {
+    knn_scan_f32_gmax<t(), t() == 4 ? 32 : 64><<<dim3((unsigned)(ix->Np / 64)), 64, 0, st>>>(
+        ix->qn, ix->gt, ix->inv_norm, ix->vals, ix->Dp, ldG, ix->n);
+  });
+  MMR_LAUNCH_CHECK();
+  launch_select<1>(st, cq, ix->vals, ldG, ldG, ix, md.f32, qc, ix->qnorm64, o);
+  MMR_LAUNCH_CHECK();
+  return MMR_OK;
+}
+
+// x3, larger chunks: the split-bf16 GEMM with the unit-max epilogue
+mmr_status search_x3_gemm(const mmr_index* ix, hipStream_t st, const float* qc, int64_t cq, const SearchOut& o,
+                          const Margins& md) {
+  const int64_t Qp = round_up(cq, 128);
+  knn_prep_queries<<<dim3((unsigned)ceil_div(Qp, 4)), dim3(256), 0, st>>>(qc, cq, ix->d, ix->qn, ix->Dp, Qp, ix->qnorm64);
+  MMR_LAUNCH_CHECK();
+  const int64_t total = Qp * ix->Dp;
+  knn_split_queries<<<dim3((unsigned)ceil_div(total, 256)), dim3(256), 0, st>>>(ix->qn, ix->Dp, total, ix->qs);
+  MMR_LAUNCH_CHECK();
+  const int tiles_m = (int)(Qp / 128), tiles_n = (int)(ix->Np / 128);
+  const int64_t ldG = ix->Np / 4;
+  knn_scores_x3_gmax<<<dim3((unsigned)(tiles_m * tiles_n)), dim3(256), 0, st>>>(
+      ix->qs, ix->gs, ix->inv_norm, ix->vals, ix->Dp, ldG, ix->n, tiles_m, tiles_n);
+  MMR_LAUNCH_CHECK();
+  launch_select<1>(st, cq, ix->vals, ldG, ldG, ix, md.x3, qc, ix->qnorm64, o);
+  MMR_LAUNCH_CHECK();
+  return MMR_OK;
+}
+
+// f32: every score to the workspace, selection over single rows
+mmr_status search_f32(const mmr_index* ix, hipStream_t st, const float* qc, int64_t cq, const SearchOut& o, const Margins& md) {
+  const int wq = cq <= 64 ? 1 : cq <= 128 ? 2 : 4;  // waves over queries; the 4 / wq others over gallery rows
+  const int64_t Qp = round_up(cq, 64 * wq);
+  knn_prep_queries<<<dim3((unsigned)ceil_div(Qp, 4)), dim3(256), 0, st>>>(qc, cq, ix->d, ix->qn, ix->Dp, Qp, ix->qnorm64);
+  MMR_LAUNCH_CHECK();
+  const int n_qblocks = (int)(Qp / (64 * wq));
+  const int n_gtiles = (int)ceil_div(ix->Np, 64 * (4 / wq));
+  const unsigned grid = (unsigned)(round_up(n_gtiles, 8) * n_qblocks);
+  pick<1, 2, 4>(wq, [&](auto w) {
+    knn_scores<w(), 4 / w()><<<grid, 256, 0, st>>>(ix->qn, ix->gal, ix->inv_norm, ix->vals, ix->Dp, ix->Np, n_gtiles, n_qblocks);
+  });
+  MMR_LAUNCH_CHECK();
+  launch_select<0>(st, cq, ix->vals, ix->Np, ix->n, ix, md.f32, qc, ix->qnorm64, o);
+  MMR_LAUNCH_CHECK();
+  return MMR_OK;
 }
 
 // Mode-specific scan copies, built when a mode first needs them (mmr_index_set_mode / the first
@@ -2482,200 +2659,35 @@ mmr_status mmr_index_search(mmr_index* ix, const float* q, int64_t nq, int32_t k
   if (s != MMR_OK) return s;
   if (ix->mode == 1 && (s = build_x3_copies(ix)) != MMR_OK) return s;  // default mode, first search
   if (ix->mode == 2 && (s = build_f16_copies(ix)) != MMR_OK) return s;  // never scan a missing copy
-  // |s_approx - s64| <= delta; threshold margin 2*delta.
-  //  f32 (knn_scores, knn_scan_f32_gmax): (Dp + 16) 2^-24 — f32 products accumulated in f32 over Dp
-  //      terms of a unit query against g/|g| (|sum| <= 1), plus the normalisations;
-  //  x3: + the dropped lo*lo bf16 terms and the bf16 rounding of the split, (3Dp + 16) 2^-24 + 4 2^-16;
-  //  f16: fp16 rounding of both unit vectors, 2 * 2^-11 relative with sum |q_k g_k| <= 1
-  //      (Cauchy-Schwarz) -> 2^-10; fp16 subnormal half-ulps (components below 2^-14 are held to
-  //      2^-25 absolute): sum_k (|q_k| + |g_k|) 2^-25 <= 2 sqrt(Dp) 2^-25 (Cauchy-Schwarz again),
-  //      computed from Dp below; f32 accumulation (Dp terms) and the f32 normalisation of both
-  //      operands (the f32-mode bound, doubled: (2Dp + 64) 2^-24).
-  const float two_delta32 = 2.0f * (float)(ix->Dp + 16) * 5.9604645e-8f;
-  const float two_delta3 = 2.0f * ((float)(3 * ix->Dp + 16) * 5.9604645e-8f + 4.0f * 1.5258789e-5f);
-  const float two_delta16 = 2.0f * (9.765625e-4f + 2.0f * sqrtf((float)ix->Dp) * 2.9802322e-8f +
-                                    (float)(2 * ix->Dp + 64) * 5.9604645e-8f);
-  //  f16 RAW (knn_scan_f16_gmax<RAW>: fp16(q) . g^ for the unnormalised q): the same terms scaled by |q|
-  //      — fp16 rounding 2^-10 |q| (Cauchy-Schwarz over |q| |g^|), g^'s subnormal half-ulps
-  //      sum |q_k| 2^-25 <= sqrt(Dp) |q| 2^-25, f32 accumulation (2Dp + 64) 2^-24 |q| — plus q's own
-  //      subnormal half-ulps sum |g^_k| 2^-25 <= sqrt(Dp) 2^-25, independent of |q|:
-  //      delta = |q| two_delta16r / 2 + two_delta16a / 2 (the selection computes |q| first).
-  const float two_delta16r = 2.0f * (9.765625e-4f + sqrtf((float)ix->Dp) * 2.9802322e-8f +
-                                     (float)(2 * ix->Dp + 64) * 5.9604645e-8f);
-  const float two_delta16a = 2.0f * sqrtf((float)ix->Dp) * 2.9802322e-8f;
+  const Margins md = margins(ix->Dp);
+  const SearchOut out{out_idx, out_score, out_score64, out_status, k};
   const int64_t chunk = chunk_queries(ix);
   for (int64_t c0 = 0; c0 < nq; c0 += chunk) {
     const int64_t cq = nq - c0 < chunk ? nq - c0 : chunk;
     const float* qc = q + c0 * ix->d;
-    int64_t* oi = out_idx + c0 * k;
-    float* os = out_score ? out_score + c0 * k : nullptr;
-    double* os64 = out_score64 ? out_score64 + c0 * k : nullptr;
-    int32_t* ost = out_status ? out_status + c0 : nullptr;
+    const SearchOut oc = out.at(c0);
     if (ix->mode == 2) {
       // fp16 scan, passes of <= 256 queries (16 * QT, QT a power of two), or on the p8 scan <= 512
       // (2-row units) / 1024 (4-row units): its query tiles share every gallery tile read (cfg5: Q =
-      // 2048 over 1M rows reads the 2 GB fp16 gallery twice instead of 8 times).  Every scan reads the
-      // tile32h fp16 image gh; rs scales raw rows (native fp16 index) by 1 / |g|.
+      // 2048 over 1M rows reads the 2 GB fp16 gallery twice instead of 8 times).
       const bool p8 = p8_ok(ix);
-      const float* rs = scan_rscale(ix);
       const bool u2 = ix->n <= (int64_t(1) << 18) || k >= 32;
       const int64_t pass = p8 ? 256 * (u2 ? 2 : kP8PairTiles) : 256;
-      for (int64_t p0 = 0; p0 < cq; p0 += pass) {
+      for (int64_t p0 = 0; p0 < cq && s == MMR_OK; p0 += pass) {
         const int64_t pq = cq - p0 < pass ? cq - p0 : pass;
-        int qt = 1;
-        while (16 * qt < pq) qt *= 2;
-        const int64_t Qp = 16 * qt;
         const float* qp = qc + p0 * ix->d;
-        const uint16_t* qh = (const uint16_t*)ix->qn;
-        float* gm = ix->vals;
-        float* bm = ix->bvals;
-        const int64_t ldG = ix->Np / 4, ldB = ix->Np / 64;
-        if (pq > 128 && p8) {
-          // 129-1024 queries: the persistent 8-phase GEMM (gemm.hip) with the unit-max epilogue —
-          // 256-query M tiles x 256-row gallery tiles, row-major fp16 queries, the tile32h gallery.
-          // (It computes all 256 query rows; at 100k x 768 it beats the LDS-ring tile scan from Q ~ 160:
-          // Q = 64 / 128 / 192 / 256: 81 / 83 / 86 / 88 us vs 62 / 69 / 96 / 100.)
-          const int tm = (int)((pq + 255) / 256);  // query tiles of this pass
-          knn_prep_queries<<<dim3(64 * tm), dim3(256), 0, st>>>(qp, pq, ix->d, ix->qn, ix->Dp, 256 * tm, ix->qnorm64, 3);
-          MMR_LAUNCH_CHECK();
-          // unit size: 2 rows halves the rows the select re-scores per candidate unit, 4 rows halves
-          // the unit maxima the scan writes (512 vs 256 MB per pass at 1M rows): 2 for small
-          // galleries or large K (cfg2 100k / K 10: select 22 -> 16 us; cfg3 1M / K 50: 104 -> 65 us for
-          // +30 us of scan), 4 for large galleries at small K (cfg5 1M / K 10: +37 us scan, -9 select)
-          const int64_t ldG8 = ix->Np / (u2 ? 2 : 4), ldB8 = ix->Np / 64;
-          MMR_CHECK_HIP(mmr::knn_scan_p8(qh, ix->gh, ix->Dp, (int)(ix->Np / 256), ix->n, gm, ldG8, bm, ldB8,
-                                         u2 ? 2 : 4, st, tm, rs));
-          if (u2)
-            launch_select<3, true>(st, pq, gm, ldG8, ldG8, ix, k, two_delta16, qp, ix->qnorm64, oi + p0 * k,
-                                   os ? os + p0 * k : nullptr, os64 ? os64 + p0 * k : nullptr, ost ? ost + p0 : nullptr,
-                                   bm, ldB8);
-          else
-            launch_select<2, true>(st, pq, gm, ldG8, ldG8, ix, k, two_delta16, qp, ix->qnorm64, oi + p0 * k,
-                                   os ? os + p0 * k : nullptr, os64 ? os64 + p0 * k : nullptr, ost ? ost + p0 : nullptr,
-                                   bm, ldB8);
-          MMR_LAUNCH_CHECK();
-          continue;
-        }
-        if (pq > 32) {
-          // 33-256 queries: the LDS-staged tile scan (64 / 128 / 256-query tiles), contiguous units
-          const int wq = pq <= 64 ? 1 : pq <= 128 ? 2 : 4;
-          const int64_t Qt = 64 * wq;
-          knn_prep_queries<<<dim3((unsigned)ceil_div(Qt, 4)), dim3(256), 0, st>>>(
-              qp, pq, ix->d, ix->qn, ix->Dp, Qt, ix->qnorm64, 2);
-          MMR_LAUNCH_CHECK();
-          const int64_t n_rt = ix->Np / 16;
-          if (wq == 1) launch_f16_tile<1, 4, 4, 4, false>(st, ix, qh, gm, bm, ldG, ldB, n_rt);
-          else if (wq == 2) launch_f16_tile<2, 4, 4, 4, false>(st, ix, qh, gm, bm, ldG, ldB, n_rt);
-          else launch_f16_tile<4, 4, 2, 8, false>(st, ix, qh, gm, bm, ldG, ldB, n_rt);
-          MMR_LAUNCH_CHECK();
-          launch_select<2, true>(st, pq, gm, ldG, ldG, ix, k, two_delta16, qp, ix->qnorm64, oi + p0 * k,
-                                 os ? os + p0 * k : nullptr, os64 ? os64 + p0 * k : nullptr, ost ? ost + p0 : nullptr,
-                                 bm, ldB);
-          MMR_LAUNCH_CHECK();
-          continue;
-        }
-        const dim3 grid((unsigned)(ix->Np / 64));
-        if (qt <= 2 && ix->d % 8 == 0 && aligned16(qp)) {
-          // <= 32 queries: the scan reads the caller's f32 rows itself (no prep launch), per-query margin
-          const int64_t nqp = pq;
-          const bool lq = ix->Dp <= 1024;
-          if (lq) {
-            const size_t lds = (size_t)qt * 16 * ix->Dp * 2;
-            const int64_t nblk = ix->Np / 64;
-            const dim3 g2((unsigned)ix->n_cu);
-            if (qt == 1) {
-              if (ix->Dp % 128 == 0)
-                knn_scan_f16_lq<1, 128, 8><<<g2, 512, lds, st>>>(qp, nqp, ix->d, ix->gh, gm, bm, ix->Dp, ldG, ldB, ix->n, nblk, ix->qnorm64, rs);
-              else
-                knn_scan_f16_lq<1, 64, 8><<<g2, 512, lds, st>>>(qp, nqp, ix->d, ix->gh, gm, bm, ix->Dp, ldG, ldB, ix->n, nblk, ix->qnorm64, rs);
-            } else {
-              knn_scan_f16_lq<2, 64, 8><<<g2, 512, lds, st>>>(qp, nqp, ix->d, ix->gh, gm, bm, ix->Dp, ldG, ldB, ix->n, nblk, ix->qnorm64, rs);
-            }
-          } else if (qt == 1) {
-            if (ix->Dp % 128 == 0)
-              knn_scan_f16_gmax<1, 128, 1, true><<<grid, 64, 0, st>>>(nullptr, qp, nqp, ix->d, ix->gh, gm, bm, ix->Dp, ldG, ldB, ix->n, rs);
-            else
-              knn_scan_f16_gmax<1, 64, 1, true><<<grid, 64, 0, st>>>(nullptr, qp, nqp, ix->d, ix->gh, gm, bm, ix->Dp, ldG, ldB, ix->n, rs);
-          } else {
-            knn_scan_f16_gmax<2, 64, 1, true><<<grid, 64, 0, st>>>(nullptr, qp, nqp, ix->d, ix->gh, gm, bm, ix->Dp, ldG, ldB, ix->n, rs);
-          }
-          MMR_LAUNCH_CHECK();
-          launch_select<1, true, true>(st, pq, gm, ldG, ldG, ix, k, two_delta16r, qp, ix->qnorm64, oi + p0 * k,
-                                       os ? os + p0 * k : nullptr, os64 ? os64 + p0 * k : nullptr,
-                                       ost ? ost + p0 : nullptr, bm, ldB, two_delta16a, lq ? ix->qnorm64 : nullptr);
-          MMR_LAUNCH_CHECK();
-          continue;
-        }
-        // <= 32 queries whose rows are not 16-B aligned / d % 8 != 0: prep + the one-wave stream
-        knn_prep_queries<<<dim3((unsigned)ceil_div(Qp, 4)), dim3(256), 0, st>>>(
-            qp, pq, ix->d, ix->qn, ix->Dp, Qp, ix->qnorm64, 2);
-        MMR_LAUNCH_CHECK();
-        if (qt == 1) {
-          if (ix->Dp % 128 == 0) knn_scan_f16_gmax<1, 128><<<grid, 64, 0, st>>>(qh, nullptr, 0, ix->d, ix->gh, gm, bm, ix->Dp, ldG, ldB, ix->n, rs);
-          else knn_scan_f16_gmax<1, 64><<<grid, 64, 0, st>>>(qh, nullptr, 0, ix->d, ix->gh, gm, bm, ix->Dp, ldG, ldB, ix->n, rs);
-        } else {
-          if (ix->Dp % 128 == 0) knn_scan_f16_gmax<2, 128><<<grid, 64, 0, st>>>(qh, nullptr, 0, ix->d, ix->gh, gm, bm, ix->Dp, ldG, ldB, ix->n, rs);
-          else knn_scan_f16_gmax<2, 64><<<grid, 64, 0, st>>>(qh, nullptr, 0, ix->d, ix->gh, gm, bm, ix->Dp, ldG, ldB, ix->n, rs);
-        }
-        MMR_LAUNCH_CHECK();
-        launch_select<1, true>(st, pq, gm, ldG, ldG, ix, k, two_delta16, qp, ix->qnorm64, oi + p0 * k,
-                               os ? os + p0 * k : nullptr, os64 ? os64 + p0 * k : nullptr, ost ? ost + p0 : nullptr,
-                               bm, ldB);
-        MMR_LAUNCH_CHECK();
+        const SearchOut op = oc.at(p0);
+        if (pq > 128 && p8) s = search_f16_p8(ix, st, qp, pq, u2, op, md);
+        else if (pq > 32) s = search_f16_tile(ix, st, qp, pq, op, md);
+        else if (ix->d % 8 == 0 && aligned16(qp)) s = search_f16_raw(ix, st, qp, pq, op, md);
+        else s = search_f16_wave(ix, st, qp, pq, op, md);
       }
-    } else if (ix->mode == 1 && cq <= kSkinnyMaxQ) {
-      // skinny scan: HBM-streaming f32 MFMA, f32-mode delta
-      const int qt = cq <= 16 ? 1 : cq <= 32 ? 2 : 4;
-      const int64_t Qp = 16 * qt;
-      knn_prep_queries<<<dim3((unsigned)ceil_div(Qp, 4)), dim3(256), 0, st>>>(
-          qc, cq, ix->d, ix->qn, ix->Dp, Qp, ix->qnorm64, 1);
-      MMR_LAUNCH_CHECK();
-      const dim3 grid((unsigned)(ix->Np / 64));
-      const int64_t ldG = ix->Np / 4;
-      if (qt == 1)
-        knn_scan_f32_gmax<1, 64><<<grid, 64, 0, st>>>(ix->qn, ix->gt, ix->inv_norm, ix->vals, ix->Dp, ldG, ix->n);
-      else if (qt == 2)
-        knn_scan_f32_gmax<2, 64><<<grid, 64, 0, st>>>(ix->qn, ix->gt, ix->inv_norm, ix->vals, ix->Dp, ldG, ix->n);
-      else
-        knn_scan_f32_gmax<4, 32><<<grid, 64, 0, st>>>(ix->qn, ix->gt, ix->inv_norm, ix->vals, ix->Dp, ldG, ix->n);
-      MMR_LAUNCH_CHECK();
-      launch_select<1>(st, cq, ix->vals, ldG, ldG, ix, k, two_delta32, qc, ix->qnorm64, oi, os, os64, ost);
-      MMR_LAUNCH_CHECK();
     } else if (ix->mode == 1) {
-      const int64_t Qp = round_up(cq, 128);
-      knn_prep_queries<<<dim3((unsigned)ceil_div(Qp, 4)), dim3(256), 0, st>>>(
-          qc, cq, ix->d, ix->qn, ix->Dp, Qp, ix->qnorm64);
-      MMR_LAUNCH_CHECK();
-      const int64_t total = Qp * ix->Dp;
-      knn_split_queries<<<dim3((unsigned)ceil_div(total, 256)), dim3(256), 0, st>>>(ix->qn, ix->Dp, total, ix->qs);
-      MMR_LAUNCH_CHECK();
-      const int tiles_m = (int)(Qp / 128), tiles_n = (int)(ix->Np / 128);
-      const int64_t ldG = ix->Np / 4;
-      knn_scores_x3_gmax<<<dim3((unsigned)(tiles_m * tiles_n)), dim3(256), 0, st>>>(
-          ix->qs, ix->gs, ix->inv_norm, ix->vals, ix->Dp, ldG, ix->n, tiles_m, tiles_n);
-      MMR_LAUNCH_CHECK();
-      launch_select<1>(st, cq, ix->vals, ldG, ldG, ix, k, two_delta3, qc, ix->qnorm64, oi, os, os64, ost);
-      MMR_LAUNCH_CHECK();
+      s = cq <= kSkinnyMaxQ ? search_x3_skinny(ix, st, qc, cq, oc, md) : search_x3_gemm(ix, st, qc, cq, oc, md);
     } else {
-      int wq, wn;
-      if (cq <= 64) { wq = 1; wn = 4; } else if (cq <= 128) { wq = 2; wn = 2; } else { wq = 4; wn = 1; }
-      const int64_t Qp = round_up(cq, 64 * wq);
-      knn_prep_queries<<<dim3((unsigned)ceil_div(Qp, 4)), dim3(256), 0, st>>>(
-          qc, cq, ix->d, ix->qn, ix->Dp, Qp, ix->qnorm64);
-      MMR_LAUNCH_CHECK();
-      const int n_qblocks = (int)(Qp / (64 * wq));
-      const int n_gtiles = (int)ceil_div(ix->Np, 64 * wn);
-      const unsigned grid = (unsigned)(round_up(n_gtiles, 8) * n_qblocks);
-      if (wq == 1)
-        knn_scores<1, 4><<<grid, 256, 0, st>>>(ix->qn, ix->gal, ix->inv_norm, ix->vals, ix->Dp, ix->Np, n_gtiles, n_qblocks);
-      else if (wq == 2)
-        knn_scores<2, 2><<<grid, 256, 0, st>>>(ix->qn, ix->gal, ix->inv_norm, ix->vals, ix->Dp, ix->Np, n_gtiles, n_qblocks);
-      else
-        knn_scores<4, 1><<<grid, 256, 0, st>>>(ix->qn, ix->gal, ix->inv_norm, ix->vals, ix->Dp, ix->Np, n_gtiles, n_qblocks);
-      MMR_LAUNCH_CHECK();
-      launch_select<0>(st, cq, ix->vals, ix->Np, ix->n, ix, k, two_delta32, qc, ix->qnorm64, oi, os, os64, ost);
-      MMR_LAUNCH_CHECK();
+      s = search_f32(ix, st, qc, cq, oc, md);
     }
+    if (s != MMR_OK) return s;
   }
   ix->ws_stream = st;
   ix->ws_used = true;

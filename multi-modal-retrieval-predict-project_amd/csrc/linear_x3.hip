@@ -133,29 +133,20 @@ extern "C" mmr_status mmr_linear_x3(const float* x, int64_t ldx, int64_t bsx, co
   if (b == 0) return MMR_OK;
   const dim3 grid((unsigned)(mmr::ceil_div(b, 32) * (cout / 32)), (unsigned)nbatch);
   hipStream_t st = mmr::as_stream(stream);
-  const bool hb = bias != nullptr, hr = residual != nullptr;
   // 8 waves per tile when the launch has fewer than 2 tiles per CU (the joint chain at B = 256:
   // 96-384 tiles) and the K range splits evenly into 8
   int nw = (cin % 256 == 0 && (int64_t)grid.x * grid.y < 512) ? 8 : 4;
   const int pin = mmr::pin_x3_waves.load(std::memory_order_relaxed);  // mmr_pin_variant (tests)
   if (pin == 4 || (pin == 8 && cin % 256 == 0)) nw = pin;
-#define X3_L(A, B_, R_)                                                                                          \
-  (nw == 8 ? linear_x3<A, B_, R_, 8><<<grid, 512, 0, st>>>(x, ldx, w_hi, w_lo, bias, residual, ldr, y, ldy, b, cin, \
-                                                         cout, bsx, bsw, bsb, bsr, bsy)                          \
-           : linear_x3<A, B_, R_, 4><<<grid, 256, 0, st>>>(x, ldx, w_hi, w_lo, bias, residual, ldr, y, ldy, b, cin, \
-                                                         cout, bsx, bsw, bsb, bsr, bsy))
-  if (act == 1) {
-    if (hb && hr) X3_L(1, true, true);
-    else if (hb) X3_L(1, true, false);
-    else if (hr) X3_L(1, false, true);
-    else X3_L(1, false, false);
-  } else {
-    if (hb && hr) X3_L(0, true, true);
-    else if (hb) X3_L(0, true, false);
-    else if (hr) X3_L(0, false, true);
-    else X3_L(0, false, false);
-  }
-#undef X3_L
+  mmr::pick<4, 8>(nw, [&](auto w) {
+    constexpr int NW = decltype(w)::value;
+    mmr::pick_flags(
+        [&](auto a, auto hb, auto hr) {
+          linear_x3<a(), hb(), hr(), NW><<<grid, 64 * NW, 0, st>>>(x, ldx, w_hi, w_lo, bias, residual, ldr, y, ldy, b,
+                                                                  cin, cout, bsx, bsw, bsb, bsr, bsy);
+        },
+        act != 0, bias != nullptr, residual != nullptr);
+  });
   MMR_LAUNCH_CHECK();
   return MMR_OK;
 }

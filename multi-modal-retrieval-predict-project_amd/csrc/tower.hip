@@ -943,20 +943,17 @@ static mmr_status layernorm_launch(const uint16_t* x, const uint16_t* r, const f
   const int cpl = (nch + lpr - 1) / lpr;                   // chunks per lane
   const int64_t rows_per_block = 4 * (64 / lpr);
   const dim3 grid((unsigned)mmr::ceil_div(rows, rows_per_block));
-#define MMR_LN2(L, N)                                                                                          \
-  (q8 ? (r ? layernorm_bf16<L, N, true, true><<<grid, 256, 0, st>>>(x, r, gamma, beta, y, rows, c, eps, alpha, q8,  \
-                                                                    q8s, kp)                                        \
-           : layernorm_bf16<L, N, false, true><<<grid, 256, 0, st>>>(x, r, gamma, beta, y, rows, c, eps, alpha, q8, \
-                                                                     q8s, kp))                                        \
-      : (r ? layernorm_bf16<L, N, true><<<grid, 256, 0, st>>>(x, r, gamma, beta, y, rows, c, eps, alpha)          \
-           : layernorm_bf16<L, N, false><<<grid, 256, 0, st>>>(x, r, gamma, beta, y, rows, c, eps, alpha)))
-#define MMR_LN(L) (cpl <= 3 ? MMR_LN2(L, 3) : (cpl <= 6 ? MMR_LN2(L, 6) : MMR_LN2(L, 8)))
-  if (lpr == 8) MMR_LN(8);
-  else if (lpr == 16) MMR_LN(16);
-  else if (lpr == 32) MMR_LN(32);
-  else MMR_LN(64);
-#undef MMR_LN
-#undef MMR_LN2
+  if (!q8) q8s = nullptr, kp = 0;  // the bf16-only forms do not read them
+  mmr::pick<8, 16, 32, 64>(lpr, [&](auto l) {
+    mmr::pick_ceil<3, 6, 8>(cpl, [&](auto n) {
+      mmr::pick_flags(
+          [&](auto add, auto fp8) {
+            layernorm_bf16<decltype(l)::value, decltype(n)::value, add(), fp8()><<<grid, 256, 0, st>>>(
+                x, r, gamma, beta, y, rows, c, eps, alpha, q8, q8s, kp);
+          },
+          r != nullptr, q8 != nullptr);
+    });
+  });
   MMR_LAUNCH_CHECK();
   return MMR_OK;
 }

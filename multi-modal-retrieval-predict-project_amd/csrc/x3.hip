@@ -827,25 +827,12 @@ mmr_status launch_attention(const char* who, AttnArgs a, int64_t nbh, bool swin,
   const size_t kv = (size_t)kbs * (krow + vrow) * 4, epi = (size_t)nwv * 32 * orow * 4;
   const size_t lds = std::max(kv, epi) + (size_t)nwv * dhp * 4 + (size_t)kbs * 4 + (swin ? 64 * 8 : 0);
   const dim3 grid((unsigned)nbh), blk(64 * nwv);
-  const int mode = swin ? 2 : (a.kmask ? 1 : 0);
-#define XM(D_, M_) x3_mha<D_, M_, false><<<grid, blk, lds, st>>>(a, kbs)
-  if (mode == 2) x3_mha<1, 2, true><<<grid, blk, lds, st>>>(a, kbs);  // lk <= 64 <= kbs (checked above)
-  else if (mode == 1) {
-    switch (dt) {
-      case 1: XM(1, 1); break;
-      case 2: XM(2, 1); break;
-      case 3: XM(3, 1); break;
-      default: XM(4, 1); break;
-    }
-  } else {
-    switch (dt) {
-      case 1: XM(1, 0); break;
-      case 2: XM(2, 0); break;
-      case 3: XM(3, 0); break;
-      default: XM(4, 0); break;
-    }
-  }
-#undef XM
+  if (swin) x3_mha<1, 2, true><<<grid, blk, lds, st>>>(a, kbs);  // lk <= 64 <= kbs (checked above)
+  else
+    mmr::pick_ceil<1, 2, 3, 4>(dt, [&](auto d) {
+      mmr::pick_flags([&](auto masked) { x3_mha<decltype(d)::value, masked(), false><<<grid, blk, lds, st>>>(a, kbs); },
+                      a.kmask != nullptr);
+    });
   MMR_LAUNCH_CHECK();
   return MMR_OK;
 }
@@ -854,15 +841,8 @@ mmr_status launch_patch_merge_v(const float* x, const float* g, const float* b, 
                                 int64_t nout, int hw, int c, float eps, hipStream_t st) {
   const int nch = (int)mmr::ceil_div(std::max(4 * c, kp), 256);
   const dim3 grid((unsigned)mmr::ceil_div(nout, 4));
-#define PMV(N_) x3_patch_merge_ln_v<N_><<<grid, 256, 0, st>>>(x, g, b, y, xs, kp, nout, hw, c, eps)
-  if (nch <= 2) PMV(2);
-  else if (nch <= 3) PMV(3);
-  else if (nch <= 4) PMV(4);
-  else if (nch <= 6) PMV(6);
-  else if (nch <= 8) PMV(8);
-  else if (nch <= 12) PMV(12);
-  else PMV(16);
-#undef PMV
+  mmr::pick_ceil<2, 3, 4, 6, 8, 12, 16>(
+      nch, [&](auto nc) { x3_patch_merge_ln_v<nc()><<<grid, 256, 0, st>>>(x, g, b, y, xs, kp, nout, hw, c, eps); });
   MMR_LAUNCH_CHECK();
   return MMR_OK;
 }
@@ -888,22 +868,12 @@ mmr_status mmr_x3_linear(const float* x, int64_t ldx, const uint16_t* w_hi, cons
   MMR_REQUIRE(ntiles < (int64_t(1) << 31), "mmr_x3_linear: too many tiles");
   const dim3 grid((unsigned)ntiles);
   hipStream_t st = mmr::as_stream(stream);
-  const bool hb = bias != nullptr, hr = residual != nullptr;
-#define X3G(A, B_, R_)                                                                                    \
-  x3_gemm<A, B_, R_><<<grid, 256, 0, st>>>(x, ldx, w_hi, w_lo, bias, residual, ldr, y, ldy, (int)m, n, k, \
-                                           tiles_n, (int)ntiles)
-  if (act == 1) {
-    if (hb && hr) X3G(1, true, true);
-    else if (hb) X3G(1, true, false);
-    else if (hr) X3G(1, false, true);
-    else X3G(1, false, false);
-  } else {
-    if (hb && hr) X3G(0, true, true);
-    else if (hb) X3G(0, true, false);
-    else if (hr) X3G(0, false, true);
-    else X3G(0, false, false);
-  }
-#undef X3G
+  mmr::pick_flags(
+      [&](auto a, auto hb, auto hr) {
+        x3_gemm<a(), hb(), hr()><<<grid, 256, 0, st>>>(x, ldx, w_hi, w_lo, bias, residual, ldr, y, ldy, (int)m, n, k,
+                                                       tiles_n, (int)ntiles);
+      },
+      act != 0, bias != nullptr, residual != nullptr);
   MMR_LAUNCH_CHECK();
   return MMR_OK;
 }

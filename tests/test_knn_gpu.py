@@ -395,6 +395,40 @@ def test_knn_f16_p8_small_galleries(N, Q):
     _exact_check(G, Qm, 10, mode="f16")
 
 
+def test_knn_f16_null_outputs_sliced_across_passes():
+    """mmr_index_search through the binding with out_score and out_status NULL: Q = 600 over 513 rows runs a
+    512-query pass on the 8-phase scan and an 88-query pass on the tile scan (wq = 2), whose outputs start at
+    query 512 — a NULL output stays NULL there and the others are offset.  Indices and f64 scores are
+    bit-equal to the call with all four outputs, and both equal the f64 oracle."""
+    from mmr_amd import _lib
+    N, D, K, Q = 513, 128, 5, 600
+    rng = np.random.default_rng(513 * 7 + 600 + 1)
+    G = rng.standard_normal((N, D), dtype=np.float32)
+    Qm = rng.standard_normal((Q, D), dtype=np.float32)
+    ix = GalleryIndex(G, mode="f16")
+    q = torch.from_numpy(Qm).cuda()
+
+    def run(with_optional):
+        idx = torch.full((Q, K), -7, dtype=torch.int64, device="cuda")
+        s64 = torch.full((Q, K), float("nan"), dtype=torch.float64, device="cuda")
+        sc = torch.empty((Q, K), dtype=torch.float32, device="cuda") if with_optional else None
+        st = torch.full((Q,), -7, dtype=torch.int32, device="cuda") if with_optional else None
+        _lib.check(_lib.lib().mmr_index_search(ix._h, _lib.ptr(q), Q, K, _lib.ptr(idx), _lib.ptr(sc), _lib.ptr(s64),
+                                               _lib.ptr(st), _lib.stream_ptr(q.device)), "mmr_index_search")
+        torch.cuda.synchronize()
+        return idx.cpu().numpy(), s64.cpu().numpy(), None if st is None else st.cpu().numpy()
+
+    i4, s4, st4 = run(True)
+    i2, s2, _ = run(False)
+    ix.close()
+    assert (st4 == 0).all()
+    np.testing.assert_array_equal(i2, i4)
+    assert s2.tobytes() == s4.tobytes()
+    ei, es = oknn.exact_topk(Qm, G, K)
+    np.testing.assert_array_equal(i4, ei)
+    np.testing.assert_allclose(s4, es, rtol=0, atol=1e-12)
+
+
 @pytest.mark.parametrize("Q", [200, 300, 700])
 def test_knn_f16_p8_four_row_units(Q):
     """Galleries above 2^18 rows at K < 32: the 8-phase GEMM scan writes 4-row unit maxima
