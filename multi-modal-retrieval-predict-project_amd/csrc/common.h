@@ -40,6 +40,10 @@ __host__ __device__ inline int64_t ceil_div(int64_t x, int64_t m) { return (x + 
 // CUs of the current device (queried once; 256 where the query fails): the persistent kernels' grid size
 int cu_count();
 
+// largest gridDim.y (and .z) a launch takes: launchers that put a count there require it, so a larger one is
+// a message and not a bare launch error
+constexpr int MAX_GRID_Y = 65535;
+
 // makes `dev` the current device for a scope
 struct DeviceGuard {
   int prev = -1;

@@ -130,6 +130,8 @@ extern "C" mmr_status mmr_linear_x3(const float* x, int64_t ldx, int64_t bsx, co
   MMR_REQUIRE(aligned16(x) && aligned16(w_hi) && aligned16(w_lo),
               "mmr_linear_x3: x / w must be 16-B aligned");
   MMR_REQUIRE(act == 0 || act == 1, "mmr_linear_x3: act=%d", act);
+  MMR_REQUIRE(nbatch <= mmr::MAX_GRID_Y, "mmr_linear_x3: nbatch=%d exceeds the grid y-dimension limit of %d", nbatch,
+              mmr::MAX_GRID_Y);
   if (b == 0) return MMR_OK;
   const dim3 grid((unsigned)(mmr::ceil_div(b, 32) * (cout / 32)), (unsigned)nbatch);
   hipStream_t st = mmr::as_stream(stream);

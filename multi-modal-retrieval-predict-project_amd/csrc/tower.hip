@@ -1170,7 +1170,8 @@ mmr_status mmr_swin_head(const uint16_t* x, const float* gamma, const float* bet
 mmr_status mmr_mean_tokens(const uint16_t* x, float* y, int32_t b, int32_t l, int32_t c,
                            void* stream) {
   mmr::clear_error();
-  MMR_REQUIRE(x && y && l > 0 && c > 0, "mmr_mean_tokens: bad arguments");
+  MMR_REQUIRE(x && y && b >= 0 && l > 0 && c > 0, "mmr_mean_tokens: bad arguments");
+  MMR_REQUIRE(b <= mmr::MAX_GRID_Y, "mmr_mean_tokens: b=%d exceeds the grid y-dimension limit of %d", b, mmr::MAX_GRID_Y);
   if (b == 0) return MMR_OK;
   mean_tokens<<<dim3((unsigned)mmr::ceil_div(c, 256), (unsigned)b), 256, 0, mmr::as_stream(stream)>>>(x, y, l, c);
   MMR_LAUNCH_CHECK();
@@ -1239,6 +1240,8 @@ mmr_status mmr_linear_f32_batched(const float* x, int64_t ldx, int64_t bsx, cons
               "mmr_linear_f32_batched: bad strides");
   MMR_REQUIRE(aligned16(x) && aligned16(w), "mmr_linear_f32_batched: x / w must be 16-B aligned");
   MMR_REQUIRE(act == 0 || act == 1, "mmr_linear_f32_batched: act=%d", act);
+  MMR_REQUIRE(nbatch <= mmr::MAX_GRID_Y, "mmr_linear_f32_batched: nbatch=%d exceeds the grid y-dimension limit of %d",
+              nbatch, mmr::MAX_GRID_Y);
   if (b == 0) return MMR_OK;
   launch_linear_f32(x, w, bias, y, b, cin, cout, act, ldx, ldy, residual, ldr, mmr::as_stream(stream), nbatch, bsx,
                     bsw, bsb, bsr, bsy);

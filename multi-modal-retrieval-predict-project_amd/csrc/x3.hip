@@ -1046,6 +1046,7 @@ mmr_status mmr_x3_mean_rows(const float* x, const float* extra, float* y, int32_
                             void* stream) {
   mmr::clear_error();
   MMR_REQUIRE(x && y && b >= 0 && l > 0 && c > 0, "mmr_x3_mean_rows: bad arguments");
+  MMR_REQUIRE(b <= mmr::MAX_GRID_Y, "mmr_x3_mean_rows: b=%d exceeds the grid y-dimension limit of %d", b, mmr::MAX_GRID_Y);
   if (b == 0) return MMR_OK;
   x3_mean_rows<<<dim3((unsigned)mmr::ceil_div(c, 256), (unsigned)b), 256, 0, mmr::as_stream(stream)>>>(x, extra, y, l,
                                                                                                       c);

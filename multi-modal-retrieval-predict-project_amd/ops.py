@@ -117,7 +117,7 @@ def linear_ln(x, w, bias, residual=None, act=0, ln_mode=0, coef=None, v1=None, v
 
 
 def rw_pack(w):
-    """bf16 W (N, K) -> RWPack, or None (K not in {64, 192, 384} or W too large for LDS parts)."""
+    """bf16 W (N, K) -> RWPack, or None (K not in {64, 192} or W too large for LDS parts)."""
     _lib.require_gpu(w)
     n, k = w.shape
     if _L().mmr_linear_rw_parts(n, k) <= 0:
