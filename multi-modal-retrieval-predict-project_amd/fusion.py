@@ -41,25 +41,13 @@ import math
 import torch
 
 from . import ops
-
-
-def _f(t, dev):
-    return t.detach().to(device=dev, dtype=torch.float32).contiguous()
-
-
-def _bf(t, dev):
-    return t.detach().to(device=dev, dtype=torch.bfloat16).contiguous()
+from .towers import _bf, _f, _w8
 
 
 def _fold(w_in, b_in, w, b):
     """(W_in, b_in) o (W, b) = (W_in W, W_in b + b_in), computed in f64."""
     w_in, b_in, w, b = (t.detach().double().cpu() for t in (w_in, b_in, w, b))
     return w_in @ w, w_in @ b + b_in
-
-
-def _w8(w):
-    """bf16 weight -> MX-fp8 operand for a plain bias GEMM (256 x 256 tiles when N % 256 == 0)."""
-    return ops.quantize_mxfp8(w, layout=2 if w.shape[0] % 256 == 0 else 1)
 
 
 class _Enhancer:
@@ -79,8 +67,8 @@ class _Enhancer:
         # MX-fp8 needs C % 256 (operand panels) and head_dim % 32 (the attention core's q8 output is
         # one 32-block per lane pair); otherwise this enhancer stays bf16
         f8 = fp8 and C % 256 == 0 and self.dh % 32 == 0
-        self.w_in8 = _w8(self.w_in) if f8 else None
-        self.w_o8 = _w8(self.w_o) if f8 else None
+        self.w_in8 = _w8(self.w_in, plain=True) if f8 else None
+        self.w_o8 = _w8(self.w_o, plain=True) if f8 else None
 
     def fp8_ok(self, rows):
         return self.w_in8 is not None and rows % 256 == 0
@@ -186,7 +174,7 @@ class FusionStack:
             L["o2_wb"] = _bf(g("attn_img2txt.out_proj.weight"), dev)
             if fp8:
                 for k in ("t_w", "p_w", "pp_w", "o2_wb"):
-                    L[k + "8"] = _w8(L[k])
+                    L[k + "8"] = _w8(L[k], plain=True)
             L["o2_w"], L["o2_b"] = _f(g("attn_img2txt.out_proj.weight"), dev), _f(g("attn_img2txt.out_proj.bias"), dev)
             L["gp_w"], L["gp_b"] = _f(g("img_global_proj.weight"), dev), _f(g("img_global_proj.bias"), dev)
             L["tp_w"], L["tp_b"] = _f(g("txt_proj.weight"), dev), _f(g("txt_proj.bias"), dev)
@@ -203,7 +191,7 @@ class FusionStack:
             self.layers.append(L)
         self.s_w, self.s_b = _bf(sd["self_attn.in_proj_weight"], dev), _f(sd["self_attn.in_proj_bias"], dev)
         # combiner QKV on MX-fp8 (its operand written by the sequence assembly itself)
-        self.s_w8 = _w8(self.s_w) if fp8 and D % 256 == 0 else None
+        self.s_w8 = _w8(self.s_w, plain=True) if fp8 and D % 256 == 0 else None
         self.s_x3 = ops.X3W(_f(sd["self_attn.in_proj_weight"], dev)) if x3 else None
         self.s_ow, self.s_ob = _f(sd["self_attn.out_proj.weight"], dev), _f(sd["self_attn.out_proj.bias"], dev)
         self.pe = _f(sd["pos_encoder.pe"][0], dev)

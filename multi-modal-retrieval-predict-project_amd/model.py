@@ -196,13 +196,7 @@ class Backbones:
 
     # fast path: bf16 hidden states + fused pooling, no f32 copies of the full token grids
     def encode_image(self, image, want_patches=True):
-        tok = self.vision.tokens(image)
-        if self.tower_dtype == "x3":
-            return self.vision.head(tok)
-        B, H, W, C = tok.shape
-        patches, glob, pool = ops.swin_head(tok.view(B, H * W, C), self.vision.norm_g, self.vision.norm_b, 1e-5,
-                                            want_patches=want_patches)
-        return glob, patches, pool
+        return self.vision.head(self.vision.tokens(image), want_patches=want_patches)
 
     def encode_text(self, input_ids, attention_mask=None):
         return self.bert.forward(input_ids, attention_mask)

@@ -2,7 +2,8 @@
 
 Weights load from reference-style state dicts (timm key names for Swin — what
 Backbones.__init__ builds with timm.create_model, fusion.py:81-110 — and HF BertModel key names
-for the text tower, fusion.py:186) and are laid out once for the device:
+for the text tower, fusion.py:186) by load_swin_blocks / load_bert_layers (shared with the x3 towers,
+towers_x3.py, which pass their own weight converter) and are laid out once for the device:
 linear weights bf16 [out][in] (QKV fused into one [3C][C] GEMM), biases / LN / rel-pos tables f32,
 the 4x4/s4 patch-embed conv as a [96][64] bf16 GEMM weight (K = 3*16 zero-padded to 64).
 
@@ -74,13 +75,13 @@ def _rows256(x):
     return rows, -(-rows // 256) * 256
 
 
-def _timed(ev, name, fn):
-    """fn() with a HIP event pair around it appended to ev[name] (ev None: just fn())."""
+def _timed(ev, name, fn, *args, **kw):
+    """fn(*args, **kw) with a HIP event pair around it appended to ev[name] (ev None: just the call)."""
     if ev is None:
-        return fn()
+        return fn(*args, **kw)
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     e0.record()
-    out = fn()
+    out = fn(*args, **kw)
     e1.record()
     ev.setdefault(name, []).append((e0, e1))
     return out
@@ -94,9 +95,9 @@ def _mlp8(h, w1_8, b1, w2_8, b2, residual=None, h8=None, ev=None):
     K = h.shape[-1]
     rows, rp = _rows256(h)
     x8 = h8 if h8 is not None else ops.quantize_mxfp8(_pad_rows(h.reshape(-1, K), rp), layout=0, kp=w1_8.kp)
-    f8 = _timed(ev, "ffn1", lambda: ops.linear_mxfp8_q8(x8, w1_8, b1, act=1))
+    f8 = _timed(ev, "ffn1", ops.linear_mxfp8_q8, x8, w1_8, b1, act=1)
     r = None if residual is None else _pad_rows(residual.reshape(rows, -1), rp)
-    y = _timed(ev, "ffn2", lambda: ops.linear_mxfp8(f8, w2_8, b2, r))
+    y = _timed(ev, "ffn2", ops.linear_mxfp8, f8, w2_8, b2, r)
     return (y if rp == rows else y[:rows]).reshape(tuple(h.shape[:-1]) + (y.shape[-1],))
 
 
@@ -124,6 +125,82 @@ def _lin(x, w, b=None, residual=None, act=0, w8=None):
     return y[:rows].reshape(tuple(x.shape[:-1]) + (y.shape[-1],))
 
 
+def _fused_stem_ok(pe_pack, image, g):
+    """The one-pass stem (conv + LayerNorm, built for Swin-T's 4 x 4 / 3 -> 96 conv) takes this image."""
+    return pe_pack is not None and image.shape[1] == 3 and image.shape[2] == image.shape[3] and (g * g) % 32 == 0
+
+
+def _text_inputs(input_ids, attention_mask, dev, max_len):
+    """(ids, mask) int64 on dev, contiguous; mask defaults to ones; L truncated to max_len
+    (max_position_embeddings, like fusion.py:315-320)."""
+    ids = input_ids.to(dev, torch.int64)
+    if attention_mask is None:
+        attention_mask = torch.ones_like(ids)
+    mask = attention_mask.to(dev, torch.int64)
+    if ids.shape[1] > max_len:
+        ids, mask = ids[:, :max_len], mask[:, :max_len]
+    return ids.contiguous(), mask.contiguous()
+
+
+def load_swin_blocks(sd, cfg, dev, conv):
+    """timm Swin state dict -> one dict per stage: "blocks" (one dict per block: the linears' "<name>_w"
+    = conv(weight, dev), f32 "<name>_b", LayerNorms "n1g" / "n1b" / "n2g" / "n2b", the block's "shift" and
+    its (heads, ws*ws, ws*ws) attention "bias" with the shift mask folded in), the stage's resolution "res"
+    and window "ws", and from stage 1 on the PatchMerging "ds_g" / "ds_b" / "ds_w".  conv is _bf (bf16
+    towers) or towers_x3._x3.  The shift / window / resolution schedule lives here only; each tower adds
+    its own packs and fp8 operands to these dicts."""
+    stages = []
+    res = cfg["img_size"] // cfg["patch"]
+    ws0 = cfg["window_size"]
+    for i, depth in enumerate(cfg["depths"]):
+        st = {"blocks": []}
+        if i > 0:
+            res //= 2
+            p = f"layers.{i}.downsample."
+            st["ds_g"], st["ds_b"] = _f(sd[p + "norm.weight"], dev), _f(sd[p + "norm.bias"], dev)
+            st["ds_w"] = conv(sd[p + "reduction.weight"], dev)
+        ws = min(ws0, res)
+        st["res"], st["ws"] = res, ws
+        for j in range(depth):
+            p = f"layers.{i}.blocks.{j}."
+            shift = 0 if (j % 2 == 0 or res <= ws0) else ws0 // 2
+            table = _f(sd[p + "attn.relative_position_bias_table"], dev)
+            st["blocks"].append({
+                "shift": shift,
+                "bias": ops.swin_attn_bias(table, cfg["num_heads"][i], ws, res, shift),
+                "n1g": _f(sd[p + "norm1.weight"], dev), "n1b": _f(sd[p + "norm1.bias"], dev),
+                "qkv_w": conv(sd[p + "attn.qkv.weight"], dev), "qkv_b": _f(sd[p + "attn.qkv.bias"], dev),
+                "proj_w": conv(sd[p + "attn.proj.weight"], dev), "proj_b": _f(sd[p + "attn.proj.bias"], dev),
+                "n2g": _f(sd[p + "norm2.weight"], dev), "n2b": _f(sd[p + "norm2.bias"], dev),
+                "fc1_w": conv(sd[p + "mlp.fc1.weight"], dev), "fc1_b": _f(sd[p + "mlp.fc1.bias"], dev),
+                "fc2_w": conv(sd[p + "mlp.fc2.weight"], dev), "fc2_b": _f(sd[p + "mlp.fc2.bias"], dev),
+            })
+        stages.append(st)
+    return stages
+
+
+def load_bert_layers(sd, cfg, dev, conv):
+    """HF BertModel state dict -> one dict per encoder layer: "qkv_w" (query | key | value stacked into one
+    [3C][C] weight), "o_w", "i_w", "f_w" = conv(weight, dev), their f32 biases "<name>_b" and the two
+    post-LayerNorms "ln1_g" / "ln1_b" / "ln2_g" / "ln2_b".  conv as in load_swin_blocks."""
+    layers = []
+    for i in range(cfg["num_hidden_layers"]):
+        p = f"encoder.layer.{i}."
+        qkv_w = torch.cat([sd[p + f"attention.self.{n}.weight"] for n in ("query", "key", "value")], 0)
+        qkv_b = torch.cat([sd[p + f"attention.self.{n}.bias"] for n in ("query", "key", "value")], 0)
+        layers.append({
+            "qkv_w": conv(qkv_w, dev), "qkv_b": _f(qkv_b, dev),
+            "o_w": conv(sd[p + "attention.output.dense.weight"], dev),
+            "o_b": _f(sd[p + "attention.output.dense.bias"], dev),
+            "ln1_g": _f(sd[p + "attention.output.LayerNorm.weight"], dev),
+            "ln1_b": _f(sd[p + "attention.output.LayerNorm.bias"], dev),
+            "i_w": conv(sd[p + "intermediate.dense.weight"], dev), "i_b": _f(sd[p + "intermediate.dense.bias"], dev),
+            "f_w": conv(sd[p + "output.dense.weight"], dev), "f_b": _f(sd[p + "output.dense.bias"], dev),
+            "ln2_g": _f(sd[p + "output.LayerNorm.weight"], dev), "ln2_b": _f(sd[p + "output.LayerNorm.bias"], dev),
+        })
+    return layers
+
+
 class SwinTower:
     """timm SwinTransformer.forward_features semantics (see oracle/towers.py for the restatement).
     fp8_stages: stages whose linears (qkv, proj, fc1, fc2 and the incoming PatchMerging reduction)
@@ -147,45 +224,22 @@ class SwinTower:
         # bf16-rounded weight, so the hi image IS the bf16 conv weight
         self.pe_pack = (ops.x3_patch_embed_pack(self.pe_w[:, :w.shape[1]].float().contiguous())
                         if self.cfg["patch"] == 4 and tuple(w.shape) == (96, 48) else None)
-        self.stages = []
-        res = self.cfg["img_size"] // self.cfg["patch"]
-        ws0 = self.cfg["window_size"]
-        for i, depth in enumerate(self.cfg["depths"]):
+        self.stages = load_swin_blocks(sd, self.cfg, dev, _bf)
+        for i, st in enumerate(self.stages):
+            fp8 = i in self.fp8_stages
             if i > 0:
-                res //= 2
-            st = {"blocks": []}
-            if i > 0:
-                p = f"layers.{i}.downsample."
-                st["ds_g"], st["ds_b"] = _f(sd[p + "norm.weight"], dev), _f(sd[p + "norm.bias"], dev)
-                st["ds_w"] = _bf(sd[p + "reduction.weight"], dev)
-                st["ds_w8"] = _w8(st["ds_w"], plain=True) if i in self.fp8_stages else None
-            ws = min(ws0, res)
-            for j in range(depth):
-                p = f"layers.{i}.blocks.{j}."
-                shift = 0 if (j % 2 == 0 or res <= ws0) else ws0 // 2
-                table = _f(sd[p + "attn.relative_position_bias_table"], dev)
-                st["blocks"].append({
-                    "shift": shift,
-                    "bias": ops.swin_attn_bias(table, self.cfg["num_heads"][i], ws, res, shift),
-                    "n1g": _f(sd[p + "norm1.weight"], dev), "n1b": _f(sd[p + "norm1.bias"], dev),
-                    "qkv_w": _bf(sd[p + "attn.qkv.weight"], dev), "qkv_b": _f(sd[p + "attn.qkv.bias"], dev),
-                    "proj_w": _bf(sd[p + "attn.proj.weight"], dev), "proj_b": _f(sd[p + "attn.proj.bias"], dev),
-                    "n2g": _f(sd[p + "norm2.weight"], dev), "n2b": _f(sd[p + "norm2.bias"], dev),
-                    "fc1_w": _bf(sd[p + "mlp.fc1.weight"], dev), "fc1_b": _f(sd[p + "mlp.fc1.bias"], dev),
-                    "fc2_w": _bf(sd[p + "mlp.fc2.weight"], dev), "fc2_b": _f(sd[p + "mlp.fc2.bias"], dev),
-                })
-                bk = st["blocks"][-1]
-                fp8 = i in self.fp8_stages
+                st["ds_w8"] = _w8(st["ds_w"], plain=True) if fp8 else None
+            # the one-kernel attention half is built for C = 96 with 3 heads of 32 and 7 x 7 windows
+            sab = (self.fused_attn and not fp8 and E * 2 ** i == 96 and self.cfg["num_heads"][i] == 3
+                   and st["ws"] == 7)
+            for bk in st["blocks"]:
                 for n in ("qkv", "proj", "fc1", "fc2"):
                     bk[n + "_w8"] = _w8(bk[n + "_w"], plain=n in ("qkv", "fc1")) if fp8 else None
                 for n in ("qkv", "proj"):  # short-K linears (stage 2): resident-weight streaming kernel
                     bk[n + "_rw"] = _rw(bk[n + "_w"]) if not fp8 else None
                 bk["mlp_pack"] = ops.swin_mlp_pack(bk["fc1_w"], bk["fc2_w"]) if self.fused_mlp and not fp8 else None
-                bk["attn_pack"] = None
-                if self.fused_attn and not fp8 and E * 2 ** i == 96 and self.cfg["num_heads"][i] == 3 and ws == 7:
-                    bk["attn_pack"] = ops.swin_attn_block_pack(bk["qkv_w"], bk["qkv_b"], bk["proj_w"], bk["proj_b"],
-                                                               bk["n1g"], bk["n1b"])
-            self.stages.append(st)
+                bk["attn_pack"] = (ops.swin_attn_block_pack(bk["qkv_w"], bk["qkv_b"], bk["proj_w"], bk["proj_b"],
+                                                            bk["n1g"], bk["n1b"]) if sab else None)
         self.norm_g, self.norm_b = _f(sd["norm.weight"], dev), _f(sd["norm.bias"], dev)
         self.num_features = E * 2 ** (len(self.cfg["depths"]) - 1)
 
@@ -193,66 +247,82 @@ class SwinTower:
         """(B,3,H,W) f32 -> (B, h, w, C) bf16 tokens BEFORE the final norm."""
         cfg = self.cfg
         image = image.to(self.device, torch.float32).contiguous()
-        B = image.shape[0]
         g = cfg["img_size"] // cfg["patch"]
-        if self.pe_pack is not None and image.shape[1] == 3 and image.shape[2] == image.shape[3] \
-                and (g * g) % 32 == 0:
+        if _fused_stem_ok(self.pe_pack, image, g):
             x = ops.patch_embed_ln_bf16(image, self.pe_pack, self.pe_b, self.pe_g, self.pe_beta, 1e-5)
         else:
             cols = ops.patch_im2col(image, cfg["patch"])
             x = (ops.linear_rw(cols, self.pe_rw, self.pe_b) if self.pe_rw is not None
                  else ops.linear(cols, self.pe_w, self.pe_b))                 # (B, g*g, E)
-            x = ops.layernorm(x, self.pe_g, self.pe_beta, 1e-5).view(B, g, g, -1)
-        ws0 = cfg["window_size"]
+            x = ops.layernorm(x, self.pe_g, self.pe_beta, 1e-5).view(image.shape[0], g, g, -1)
         for i, st in enumerate(self.stages):
             if i > 0:
-                w8 = st["ds_w8"]
-                B, H2 = x.shape[0], x.shape[1] // 2
-                if (w8 is not None and (B * H2 * H2) % 256 == 0 and w8.kp == 4 * x.shape[-1]
-                        and w8.kp <= 2048):  # the gather + LN writes the reduction's fp8 operand
-                    _, m8 = ops.patch_merge_ln_q8(x, st["ds_g"], st["ds_b"], 1e-5)
-                    x = ops.linear_mxfp8(m8, w8, None, lead=(B, H2, H2))
-                else:
-                    x = _lin(ops.patch_merge_ln(x, st["ds_g"], st["ds_b"], 1e-5), st["ds_w"], w8=w8)
+                x = self._downsample(x, st)
             H = x.shape[1]
-            C = x.shape[-1]
             heads = cfg["num_heads"][i]
-            ws = min(ws0, H)
-            for j, bk in enumerate(st["blocks"]):
-                if bk["attn_pack"] is not None:
-                    x = ops.swin_attn_block(x, bk["attn_pack"], bk["bias"], ws, bk["shift"], 1e-5)
-                elif _ln8_ok(x, bk["qkv_w8"]):  # fp8 stage: the LN emits the QKV operand (no bf16 rows)
-                    _, h8 = ops.layernorm_q8(x, None, bk["n1g"], bk["n1b"], 1e-5, kp=bk["qkv_w8"].kp, want_y=False)
-                    qkv = ops.linear_mxfp8(h8, bk["qkv_w8"], bk["qkv_b"], lead=tuple(x.shape[:-1]))
-                    # the attention core writes the proj operand (no bf16 rows, no quantise pass)
-                    a8 = ops.swin_window_attention_q8(qkv, bk["bias"], H, heads, ws, bk["shift"], kp=bk["proj_w8"].kp)
-                    x = ops.linear_mxfp8(a8, bk["proj_w8"], bk["proj_b"], x, lead=tuple(x.shape[:-1]))
-                else:
-                    h = ops.layernorm(x, bk["n1g"], bk["n1b"], 1e-5)
-                    qkv = (ops.linear_rw(h, bk["qkv_rw"], bk["qkv_b"]) if bk["qkv_rw"] is not None
-                           else _lin(h, bk["qkv_w"], bk["qkv_b"], w8=bk["qkv_w8"]))
-                    a = ops.swin_window_attention(qkv, bk["bias"], H, heads, ws, bk["shift"])
-                    x = (ops.linear_rw(a, bk["proj_rw"], bk["proj_b"], residual=x) if bk["proj_rw"] is not None
-                         else _lin(a, bk["proj_w"], bk["proj_b"], residual=x, w8=bk["proj_w8"]))
-                if bk["mlp_pack"] is not None:
-                    x = ops.swin_mlp(x, bk["n2g"], bk["n2b"], bk["mlp_pack"], bk["fc1_b"], bk["fc2_b"], 1e-5)
-                elif _ln8_ok(x, bk["fc1_w8"]) and bk["fc1_w8"].layout == 2:
-                    _, h8 = ops.layernorm_q8(x, None, bk["n2g"], bk["n2b"], 1e-5, kp=bk["fc1_w8"].kp, want_y=False)
-                    x = _mlp8(x, bk["fc1_w8"], bk["fc1_b"], bk["fc2_w8"], bk["fc2_b"], residual=x, h8=h8)
-                else:
-                    h = ops.layernorm(x, bk["n2g"], bk["n2b"], 1e-5)
-                    if bk["fc1_w8"] is not None and bk["fc1_w8"].layout == 2:
-                        x = _mlp8(h, bk["fc1_w8"], bk["fc1_b"], bk["fc2_w8"], bk["fc2_b"], residual=x)
-                    else:
-                        h = _lin(h, bk["fc1_w"], bk["fc1_b"], act=1, w8=bk["fc1_w8"])
-                        x = _lin(h, bk["fc2_w"], bk["fc2_b"], residual=x, w8=bk["fc2_w8"])
-            del C
+            ws = min(cfg["window_size"], H)
+            for bk in st["blocks"]:
+                x = self._mlp_half(self._attn_half(x, bk, H, heads, ws), bk)
         return x
+
+    def _downsample(self, x, st):
+        """PatchMerging into stage st: gather 2 x 2 + LayerNorm(4C) -> reduction GEMM (no bias)."""
+        w8 = st["ds_w8"]
+        B, H2 = x.shape[0], x.shape[1] // 2
+        if (w8 is not None and (B * H2 * H2) % 256 == 0 and w8.kp == 4 * x.shape[-1]
+                and w8.kp <= 2048):  # the gather + LN writes the reduction's fp8 operand
+            _, m8 = ops.patch_merge_ln_q8(x, st["ds_g"], st["ds_b"], 1e-5)
+            return ops.linear_mxfp8(m8, w8, None, lead=(B, H2, H2))
+        return _lin(ops.patch_merge_ln(x, st["ds_g"], st["ds_b"], 1e-5), st["ds_w"], w8=w8)
+
+    def _attn_half(self, x, bk, H, heads, ws):
+        """x + proj(W-MSA(norm1(x))) of one block: one kernel where the block holds attn_pack (C = 96), the
+        fp8 chain where the LayerNorm can emit the QKV operand, else LN -> QKV -> window attention -> proj
+        (resident-weight linears at short K, else the bf16 / fp8 GEMM)."""
+        if bk["attn_pack"] is not None:
+            return ops.swin_attn_block(x, bk["attn_pack"], bk["bias"], ws, bk["shift"], 1e-5)
+        if _ln8_ok(x, bk["qkv_w8"]):  # fp8 stage: the LN emits the QKV operand (no bf16 rows)
+            lead = tuple(x.shape[:-1])
+            _, h8 = ops.layernorm_q8(x, None, bk["n1g"], bk["n1b"], 1e-5, kp=bk["qkv_w8"].kp, want_y=False)
+            qkv = ops.linear_mxfp8(h8, bk["qkv_w8"], bk["qkv_b"], lead=lead)
+            # the attention core writes the proj operand (no bf16 rows, no quantise pass)
+            a8 = ops.swin_window_attention_q8(qkv, bk["bias"], H, heads, ws, bk["shift"], kp=bk["proj_w8"].kp)
+            return ops.linear_mxfp8(a8, bk["proj_w8"], bk["proj_b"], x, lead=lead)
+        h = ops.layernorm(x, bk["n1g"], bk["n1b"], 1e-5)
+        qkv = (ops.linear_rw(h, bk["qkv_rw"], bk["qkv_b"]) if bk["qkv_rw"] is not None
+               else _lin(h, bk["qkv_w"], bk["qkv_b"], w8=bk["qkv_w8"]))
+        a = ops.swin_window_attention(qkv, bk["bias"], H, heads, ws, bk["shift"])
+        if bk["proj_rw"] is not None:
+            return ops.linear_rw(a, bk["proj_rw"], bk["proj_b"], residual=x)
+        return _lin(a, bk["proj_w"], bk["proj_b"], residual=x, w8=bk["proj_w8"])
+
+    def _mlp_half(self, x, bk):
+        """x + fc2(GELU(fc1(norm2(x)))) of one block: one kernel where the block holds mlp_pack, else the fp8
+        pair with fc1 emitting fc2's operand (the LayerNorm emitting fc1's where it can), else two GEMMs."""
+        if bk["mlp_pack"] is not None:
+            return ops.swin_mlp(x, bk["n2g"], bk["n2b"], bk["mlp_pack"], bk["fc1_b"], bk["fc2_b"], 1e-5)
+        w8 = bk["fc1_w8"]
+        if _ln8_ok(x, w8) and w8.layout == 2:
+            _, h8 = ops.layernorm_q8(x, None, bk["n2g"], bk["n2b"], 1e-5, kp=w8.kp, want_y=False)
+            return _mlp8(x, w8, bk["fc1_b"], bk["fc2_w8"], bk["fc2_b"], residual=x, h8=h8)
+        h = ops.layernorm(x, bk["n2g"], bk["n2b"], 1e-5)
+        if w8 is not None and w8.layout == 2:
+            return _mlp8(h, w8, bk["fc1_b"], bk["fc2_w8"], bk["fc2_b"], residual=x)
+        h = _lin(h, bk["fc1_w"], bk["fc1_b"], act=1, w8=w8)
+        return _lin(h, bk["fc2_w"], bk["fc2_b"], residual=x, w8=bk["fc2_w8"])
 
     def forward_features(self, image):
         """timm forward_features: (B, h, w, C) NHWC after the final norm (bf16)."""
         x = self.tokens(image)
         return ops.layernorm(x, self.norm_g, self.norm_b, 1e-5)
+
+    def head(self, tok, want_patches=True):
+        """Backbones.forward image branch (fusion.py:259-265) from pre-norm tokens (B, h, w, C), one fused
+        pass: (img_global, img_patches or None, pool) f32 — pool = mean over [global; patches]."""
+        B, H, W, C = tok.shape
+        patches, glob, pool = ops.swin_head(tok.view(B, H * W, C), self.norm_g, self.norm_b, 1e-5,
+                                            want_patches=want_patches)
+        return glob, patches, pool
 
 
 def _ln_fold(w, b, gamma, beta):
@@ -278,22 +348,8 @@ class BertTower:
         self.pos = _f(sd["embeddings.position_embeddings.weight"], dev)
         self.type0 = _f(sd["embeddings.token_type_embeddings.weight"][0], dev)
         self.eg, self.eb = _f(sd["embeddings.LayerNorm.weight"], dev), _f(sd["embeddings.LayerNorm.bias"], dev)
-        self.layers = []
-        for i in range(self.cfg["num_hidden_layers"]):
-            p = f"encoder.layer.{i}."
-            qkv_w = torch.cat([sd[p + f"attention.self.{n}.weight"] for n in ("query", "key", "value")], 0)
-            qkv_b = torch.cat([sd[p + f"attention.self.{n}.bias"] for n in ("query", "key", "value")], 0)
-            self.layers.append({
-                "qkv_w": _bf(qkv_w, dev), "qkv_b": _f(qkv_b, dev),
-                "o_w": _bf(sd[p + "attention.output.dense.weight"], dev),
-                "o_b": _f(sd[p + "attention.output.dense.bias"], dev),
-                "ln1_g": _f(sd[p + "attention.output.LayerNorm.weight"], dev),
-                "ln1_b": _f(sd[p + "attention.output.LayerNorm.bias"], dev),
-                "i_w": _bf(sd[p + "intermediate.dense.weight"], dev), "i_b": _f(sd[p + "intermediate.dense.bias"], dev),
-                "f_w": _bf(sd[p + "output.dense.weight"], dev), "f_b": _f(sd[p + "output.dense.bias"], dev),
-                "ln2_g": _f(sd[p + "output.LayerNorm.weight"], dev), "ln2_b": _f(sd[p + "output.LayerNorm.bias"], dev),
-            })
-            ly = self.layers[-1]
+        self.layers = load_bert_layers(sd, self.cfg, dev, _bf)
+        for ly in self.layers:
             for n in ("qkv", "o", "i", "f"):
                 ly[n + "_w8"] = _w8(ly[n + "_w"], plain=True) if fp8 else None
         self.hidden = self.word.shape[1]
@@ -314,108 +370,89 @@ class BertTower:
         # ride torch's current stream = the launch stream)
         self.gemm_events = None
 
-    def _forward_folded(self, ids, mask, gemm_ln):
+    def forward(self, input_ids, attention_mask=None):
+        """(B, L) ids/mask -> (B, L, C) bf16 last_hidden_state.  L is truncated to
+        max_position_embeddings like fusion.py:315-320.  Picks the layer stack: LayerNorm-folded bf16
+        (_forward_folded), the fp8 fast path (_forward_fp8), else _forward_plain."""
+        ids, mask = _text_inputs(input_ids, attention_mask, self.device, self.cfg["max_position_embeddings"])
+        rows, C = ids.numel(), self.hidden
+        if self.ln_fold and rows % 256 == 0 and ops.linear_ln_parts(rows, C, 2) > 0:
+            return self._forward_folded(ids, mask)
+        if (self.fp8 and C % 256 == 0 and C <= 1024 and rows % 256 == 0
+                and all(ly["qkv_w8"].kp == C and ly["i_w8"].layout == 2 for ly in self.layers)):
+            return self._forward_fp8(ids, mask)
+        return self._forward_plain(ids, mask)
+
+    def _forward_folded(self, ids, mask):
         """The bf16 layer stack with the LayerNorms folded into the GEMMs (see __init__): per layer
         QKV (fold LN2 of the previous layer) -> attention -> O-proj (+ LN2(previous raw output),
         statistics) -> FFN1 (fold LN1, GELU) -> FFN2 (+ LN1(raw O-proj output), statistics); one
-        LayerNorm at the end materialises last_hidden_state.  Same maths as forward's unfused path:
+        LayerNorm at the end materialises last_hidden_state.  Same maths as _forward_plain:
         HF BertLayer (reference fusion.py:322-325), the normalised rows just never round-trip HBM."""
         heads = self.cfg["num_attention_heads"]
         C, eps = self.hidden, 1e-12
+        ev, gemm_ln = self.gemm_events, ops.linear_ln
         h0 = ops.bert_embed(ids, self.word, self.pos, self.type0, self.eg, self.eb, eps)
         y2 = cf2 = None
         for i, ly in enumerate(self.layers):
             if i == 0:
-                qkv, _ = gemm_ln("qkv", h0, ly["qkv_w"], ly["qkv_b"], plain=True)
+                qkv = _timed(ev, "qkv", _lin, h0, ly["qkv_w"], ly["qkv_b"])
             else:
-                qkv, _ = gemm_ln("qkv", y2, ly["qkv_wf"], ly["qkv_d"], ln_mode=1, coef=cf2, v1=ly["qkv_c"])
+                qkv, _ = _timed(ev, "qkv", gemm_ln, y2, ly["qkv_wf"], ly["qkv_d"], ln_mode=1, coef=cf2, v1=ly["qkv_c"])
             ctx = ops.bert_attention(qkv, mask, heads, C // heads)
             if i == 0:
-                y1, st1 = gemm_ln("o", ctx, ly["o_w"], ly["o_b"], residual=h0, want_stats=True)
+                y1, st1 = _timed(ev, "o", gemm_ln, ctx, ly["o_w"], ly["o_b"], residual=h0, want_stats=True)
             else:
                 prev = self.layers[i - 1]
-                y1, st1 = gemm_ln("o", ctx, ly["o_w"], ly["o_b"], residual=y2, ln_mode=2, coef=cf2,
+                y1, st1 = _timed(ev, "o", gemm_ln, ctx, ly["o_w"], ly["o_b"], residual=y2, ln_mode=2, coef=cf2,
                                   v1=prev["ln2_g"], v2=prev["ln2_b"], want_stats=True)
             cf1 = ops.ln_row_coef(st1, C, eps)
-            f1, _ = gemm_ln("ffn1", y1, ly["i_wf"], ly["i_d"], act=1, ln_mode=1, coef=cf1, v1=ly["i_c"])
-            y2, st2 = gemm_ln("ffn2", f1, ly["f_w"], ly["f_b"], residual=y1, ln_mode=2, coef=cf1, v1=ly["ln1_g"],
-                              v2=ly["ln1_b"], want_stats=True)
+            f1, _ = _timed(ev, "ffn1", gemm_ln, y1, ly["i_wf"], ly["i_d"], act=1, ln_mode=1, coef=cf1, v1=ly["i_c"])
+            y2, st2 = _timed(ev, "ffn2", gemm_ln, f1, ly["f_w"], ly["f_b"], residual=y1, ln_mode=2, coef=cf1,
+                             v1=ly["ln1_g"], v2=ly["ln1_b"], want_stats=True)
             cf2 = ops.ln_row_coef(st2, C, eps)
         last = self.layers[-1]
         return ops.layernorm(y2, last["ln2_g"], last["ln2_b"], eps)
 
-    def forward(self, input_ids, attention_mask=None):
-        """(B, L) ids/mask -> (B, L, C) bf16 last_hidden_state.  L is truncated to
-        max_position_embeddings like fusion.py:315-320."""
-        cfg = self.cfg
-        ids = input_ids.to(self.device, torch.int64)
-        if attention_mask is None:
-            attention_mask = torch.ones_like(ids)
-        mask = attention_mask.to(self.device, torch.int64)
-        max_len = cfg["max_position_embeddings"]
-        if ids.shape[1] > max_len:
-            ids, mask = ids[:, :max_len], mask[:, :max_len]
-        ids, mask = ids.contiguous(), mask.contiguous()
-        heads = cfg["num_attention_heads"]
-        ev = self.gemm_events
-        rows, C = ids.numel(), self.hidden
-        # fp8 fast path: every LayerNorm also emits the next GEMM's MX-fp8 operand (the embedding
-        # LayerNorm the first QKV's), FFN1 emits FFN2's
-        fast8 = (self.fp8 and C % 256 == 0 and C <= 1024 and rows % 256 == 0
-                 and all(ly["qkv_w8"].kp == C and ly["i_w8"].layout == 2 for ly in self.layers))
-
-        def gemm(name, x, w, b, act=0, w8=None):
-            if ev is None:
-                return _lin(x, w, b, act=act, w8=w8)
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            y = _lin(x, w, b, act=act, w8=w8)
-            e1.record()
-            ev.setdefault(name, []).append((e0, e1))
-            return y
-
-        if self.ln_fold and rows % 256 == 0 and ops.linear_ln_parts(rows, C, 2) > 0:
-            def gemm_ln(name, x, w, b, plain=False, **kw):
-                if plain:
-                    return gemm(name, x, w, b), None
-                if ev is None:
-                    return ops.linear_ln(x, w, b, **kw)
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-                out = ops.linear_ln(x, w, b, **kw)
-                e1.record()
-                ev.setdefault(name, []).append((e0, e1))
-                return out
-            return self._forward_folded(ids, mask, gemm_ln)
-        if fast8:
-            h, h8 = ops.bert_embed_q8(ids, self.word, self.pos, self.type0, self.eg, self.eb, 1e-12)
-        else:
-            h, h8 = ops.bert_embed(ids, self.word, self.pos, self.type0, self.eg, self.eb, 1e-12), None
+    def _forward_fp8(self, ids, mask):
+        """The fp8 fast path (rows a multiple of 256): every LayerNorm also emits the next GEMM's MX-fp8
+        operand (the embedding LayerNorm the first QKV's), the attention O-proj's, FFN1 FFN2's.
+        gemm_events, when set, wrap the very launches the untimed forward makes."""
+        heads, ev = self.cfg["num_attention_heads"], self.gemm_events
+        dh = self.hidden // heads
+        h, h8 = ops.bert_embed_q8(ids, self.word, self.pos, self.type0, self.eg, self.eb, 1e-12)
         lead = tuple(h.shape[:-1])
         for ly in self.layers:
-            if fast8:
-                # (events, when set, time the very kernels the timed steps run)
-                qkv = _timed(ev, "qkv", lambda: ops.linear_mxfp8(h8, ly["qkv_w8"], ly["qkv_b"], lead=lead))
-                dh = self.hidden // heads
-                if dh % 32 == 0 and ly["o_w8"].kp == self.hidden:  # the attention emits O-proj's operand
-                    _, c8 = ops.bert_attention(qkv, mask, heads, dh, q8=True, bf16=False)
-                    a = _timed(ev, "o", lambda: ops.linear_mxfp8(c8, ly["o_w8"], ly["o_b"], lead=lead))
-                else:
-                    ctx = ops.bert_attention(qkv, mask, heads, dh)
-                    a = gemm("o", ctx, ly["o_w"], ly["o_b"], w8=ly["o_w8"])
-                h, h8 = ops.layernorm_q8(a, h, ly["ln1_g"], ly["ln1_b"], 1e-12)
-                f = _mlp8(h, ly["i_w8"], ly["i_b"], ly["f_w8"], ly["f_b"], h8=h8, ev=ev)
-                h, h8 = ops.layernorm_q8(f, h, ly["ln2_g"], ly["ln2_b"], 1e-12)
-                continue
-            qkv = gemm("qkv", h, ly["qkv_w"], ly["qkv_b"], w8=ly["qkv_w8"])
+            qkv = _timed(ev, "qkv", ops.linear_mxfp8, h8, ly["qkv_w8"], ly["qkv_b"], lead=lead)
+            if dh % 32 == 0 and ly["o_w8"].kp == self.hidden:  # the attention emits O-proj's operand
+                _, c8 = ops.bert_attention(qkv, mask, heads, dh, q8=True, bf16=False)
+                a = _timed(ev, "o", ops.linear_mxfp8, c8, ly["o_w8"], ly["o_b"], lead=lead)
+            else:
+                ctx = ops.bert_attention(qkv, mask, heads, dh)
+                a = _timed(ev, "o", _lin, ctx, ly["o_w"], ly["o_b"], w8=ly["o_w8"])
+            h, h8 = ops.layernorm_q8(a, h, ly["ln1_g"], ly["ln1_b"], 1e-12)
+            f = _mlp8(h, ly["i_w8"], ly["i_b"], ly["f_w8"], ly["f_b"], h8=h8, ev=ev)
+            h, h8 = ops.layernorm_q8(f, h, ly["ln2_g"], ly["ln2_b"], 1e-12)
+        return h
+
+    def _forward_plain(self, ids, mask):
+        """HF BertLayer as written: GEMMs (bf16, or MX-fp8 on zero-padded rows where the layer holds w8) with
+        the post-LN residual adds in the LayerNorm kernel."""
+        heads, ev = self.cfg["num_attention_heads"], self.gemm_events
+        # a set gemm_events selects FFN1 / FFN2 as two separately quantised GEMMs here on purpose (bench.py's
+        # per-GEMM roofline reads that chain); only the untimed forward takes the _mlp8 pair
+        pair8 = ev is None
+        h = ops.bert_embed(ids, self.word, self.pos, self.type0, self.eg, self.eb, 1e-12)
+        for ly in self.layers:
+            qkv = _timed(ev, "qkv", _lin, h, ly["qkv_w"], ly["qkv_b"], w8=ly["qkv_w8"])
             ctx = ops.bert_attention(qkv, mask, heads, self.hidden // heads)
-            a = gemm("o", ctx, ly["o_w"], ly["o_b"], w8=ly["o_w8"])
+            a = _timed(ev, "o", _lin, ctx, ly["o_w"], ly["o_b"], w8=ly["o_w8"])
             h = ops.add_layernorm(a, h, ly["ln1_g"], ly["ln1_b"], 1e-12)
-            if ly["i_w8"] is not None and ly["i_w8"].layout == 2 and ev is None:
+            if pair8 and ly["i_w8"] is not None and ly["i_w8"].layout == 2:
                 f = _mlp8(h, ly["i_w8"], ly["i_b"], ly["f_w8"], ly["f_b"])  # FFN1 emits FFN2's fp8 operand
             else:
-                f = gemm("ffn1", h, ly["i_w"], ly["i_b"], act=1, w8=ly["i_w8"])
-                f = gemm("ffn2", f, ly["f_w"], ly["f_b"], w8=ly["f_w8"])
+                f = _timed(ev, "ffn1", _lin, h, ly["i_w"], ly["i_b"], act=1, w8=ly["i_w8"])
+                f = _timed(ev, "ffn2", _lin, f, ly["f_w"], ly["f_b"], w8=ly["f_w8"])
             h = ops.add_layernorm(f, h, ly["ln2_g"], ly["ln2_b"], 1e-12)
         return h
 
