@@ -806,6 +806,66 @@ mmr_status mmr_cls_eval(const float* scores, int64_t lds, const uint64_t* label_
                         const float* thresholds, int64_t* counts, double* ap_sum, float* best_thr, double* best_f1,
                         int64_t* confusion, int64_t* nonfinite, void* work, void* stream);
 
+/* ---------------------------------------------------------------- attention explanations */
+/* The attention family of the reference's ExplanationEngine.explain (src/Model/explain.py:825-947) for every sample
+ * of a batch, csrc/explain.hip.  Inputs, f32, rows at unit column stride, batch / row strides in elements:
+ * txt2img (b, lt, np), img2txt (b, np, lt), comb (b, lc_rows, lc_cols) — each may be NULL (its outputs are then not
+ * written); t = the text length (txt_feats.shape[1]).  Per sample, every mean an f64 sum in a fixed order rounded to
+ * f32 once, the rest f32 without contraction:
+ *   p_txt (b, np) = column mean of txt2img;  t_img (b, lt) = column mean of img2txt
+ *   p_comb (b, np), lc >= np only: lc == np the column mean, else the window of np consecutive columns with the
+ *     largest mass (f64 column sums, ties: the lowest offset) — all zeros when max / (total + 1e-12) < 0.06, else
+ *     the chosen columns' means
+ *   t_comb (b, ltc), ltc = min(t, lc): lc == t the column mean; lc > t the same search over row sums (windows of t
+ *     rows, ratio 0.0) and the chosen rows' means; lc < t the row means min-max normalised to [0, 1] (the uniform
+ *     1 / lc when |max - min| < 1e-8)
+ *   final_patch (b, np) = minmax(0.6 p_txt + 0.4 p_comb), or of the one that exists; final_token (b, min(lt, ltc))
+ *     the same from t_img and t_comb trimmed to the shorter (lengths lt / ltc when only one exists);
+ *     minmax(x) = (x - min) / ((max - min) + 1e-8f)
+ *   map_txt2img, map_comb, map_final (b, h, w), each may be NULL: compute_attention_map of p_txt, p_comb,
+ *     final_patch — minmax, viewed G x G, bilinear to (h, w) as F.interpolate(align_corners=False)
+ *   offsets (b, 2) int32 = the chosen column / row offsets (0 for a plain mean, -1 where no vector)
+ *   comb_absmax (b, 2) = max |p_comb|, max |t_comb| (the caller drops comb_img at <= 1e-8 and refuses a t_comb
+ *     that is all <= 1e-7: steps 3-5 of compute_comb_token_vector are not built)
+ *   nonfinite (1) int64 = the number of NaN / infinite entries of p_txt, t_img, p_comb, t_comb
+ * MMR_ERR_INVALID before any launch: np outside 1..1024, or not a perfect square with a heat map asked for; lt or lc
+ * outside 1..4096; comb not square; h * w outside 1..65536 with a heat map; a heat map not 16-B aligned; a NULL
+ * output for a map that is given.  work: mmr_explain_attention_work_bytes(b, lt, np, lc) bytes (0: shape not
+ * taken), 16-B aligned, needed with comb.  No float atomics: two runs give identical bytes. */
+int64_t mmr_explain_attention_work_bytes(int32_t b, int32_t lt, int32_t np, int32_t lc);
+mmr_status mmr_explain_attention(const float* txt2img, int64_t t2i_bs, int64_t t2i_rs, const float* img2txt,
+                                 int64_t i2t_bs, int64_t i2t_rs, const float* comb, int64_t comb_bs, int64_t comb_rs,
+                                 int32_t b, int32_t lt, int32_t np, int32_t lc_rows, int32_t lc_cols, int32_t t,
+                                 int32_t h, int32_t w, float* p_txt, float* t_img, float* p_comb, float* t_comb,
+                                 float* final_patch, float* final_token, float* map_txt2img, float* map_comb,
+                                 float* map_final, int32_t* offsets, float* comb_absmax, int64_t* nonfinite,
+                                 void* work, void* stream);
+
+/* ---------------------------------------------------------------- map alignment */
+/* The reference's compare_maps (src/Helpers/helper.py:173-209) for p pairs (pa[i], pb[i]) (int64) over n maps of hw
+ * f32 pixels at stride ld, csrc/map_align.hip.  -0 == +0; k[j] = max(1, int(hw * frac_j)) for nf <= 4 fractions.
+ * Per map:
+ *   ranks2 (n, hw) uint32 = 2 x the average rank (scipy rankdata) of every pixel
+ *   thresholds (n, nf) f32 = the k[j]-th largest value;  constant (n) int32 = all pixels equal
+ *   mean (n), ssd (n) f64 = the mean and the sum of (x - mean)^2, summed in a fixed order
+ * Per pair:
+ *   pearson (p) f64 = sum (a - mean_a)(b - mean_b) / sqrt(ssd_a ssd_b)
+ *   rank_sums (p, 3) int64 = S_ab, S_aa, S_bb of the centred doubled ranks c = ranks2 - (hw + 1) (exact)
+ *   spearman (p) f64 = S_ab / sqrt(S_aa S_bb) (exactly 1 for a self-pair); pearson = spearman = 0.0 when either
+ *     map is constant
+ *   inter_union (p, nf, 2) int64 = the counts of (a >= ta_j) & (b >= tb_j) and of (a >= ta_j) | (b >= tb_j)
+ *   skipped (p) int32 = 1 where pa[i] or pb[i] is outside [0, n): that pair's outputs are zeros
+ * nonfinite (1) int64 = the number of NaN / infinite pixels (the other outputs are meaningless when it is not 0).
+ * MMR_ERR_INVALID before any launch: n outside 1..65536, hw outside 1..65536, n * hw >= 2^31, k[j] outside 1..hw.
+ * work: mmr_map_alignment_work_bytes(n, hw) bytes (0: shape not taken), 16-B aligned.  Integer results, order
+ * statistics and fixed-order f64 sums only: two runs give identical bytes. */
+int64_t mmr_map_alignment_work_bytes(int64_t n, int32_t hw);
+mmr_status mmr_map_alignment(const float* maps, int64_t ld, int64_t n, int32_t hw, const int64_t* pa,
+                             const int64_t* pb, int64_t p, int32_t nf, int32_t k0, int32_t k1, int32_t k2, int32_t k3,
+                             uint32_t* ranks2, float* thresholds, int32_t* constant, double* mean, double* ssd,
+                             double* pearson, double* spearman, int64_t* rank_sums, int64_t* inter_union,
+                             int32_t* skipped, int64_t* nonfinite, void* work, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -143,6 +143,13 @@ SIGNATURES = {
                             c_i32, c_i32, c_f32, c_vp],
     "mmr_cls_eval_work_bytes": [c_i64, c_i32],
     "mmr_cls_eval": [c_vp, c_i64, c_vp, c_i64, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp],
+    "mmr_explain_attention_work_bytes": [c_i32, c_i32, c_i32, c_i32],
+    "mmr_explain_attention": [c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, c_i32, c_i32, c_i32, c_i32,
+                              c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
+                              c_vp, c_vp, c_vp, c_vp],
+    "mmr_map_alignment_work_bytes": [c_i64, c_i32],
+    "mmr_map_alignment": [c_vp, c_i64, c_i64, c_i32, c_vp, c_vp, c_i64, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp,
+                          c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp],
 }
 _RESTYPES = {"mmr_last_error": ctypes.c_char_p, "mmr_version": ctypes.c_int, "mmr_max_k": ctypes.c_int,
              "mmr_linear_bf16_variant": ctypes.c_int32, "mmr_linear_bf16_n_variants": ctypes.c_int32,
@@ -154,7 +161,8 @@ _RESTYPES = {"mmr_last_error": ctypes.c_char_p, "mmr_version": ctypes.c_int, "mm
              "mmr_x3_swin_attn_block_pack_bytes": ctypes.c_int64,
              "mmr_classifier_pack_bytes": ctypes.c_int64, "mmr_classifier_work_bytes": ctypes.c_int64,
              "mmr_index_rank_work_bytes": ctypes.c_int64, "mmr_cls_eval_work_bytes": ctypes.c_int64,
-             "mmr_index_list_diversity_work_bytes": ctypes.c_int64}
+             "mmr_index_list_diversity_work_bytes": ctypes.c_int64,
+             "mmr_explain_attention_work_bytes": ctypes.c_int64, "mmr_map_alignment_work_bytes": ctypes.c_int64}
 
 ABI_VERSION = 2  # mmr_version() this binding is written against (2: the full-ranking evaluation entry points)
 

@@ -44,7 +44,6 @@ namespace {
 
 using mmr::aligned16;
 
-constexpr int CE_WMAX = 4096;  // sort chunks (waves) per pass at most
 constexpr int CE_TILE = 1024;  // curve tile: 256 threads x 4 consecutive keys
 constexpr int CE_MAXC = 64;
 
@@ -74,110 +73,7 @@ __global__ __launch_bounds__(256) void ce_build_keys(const uint32_t* __restrict_
 }
 
 // ------------------------------------------------------------------------------------------------ radix sort
-__global__ __launch_bounds__(64) void ce_hist(const uint64_t* __restrict__ in, int64_t m, int64_t per, int shift,
-                                              uint32_t* __restrict__ hist, int W) {
-  __shared__ uint32_t h[256];
-  const int lane = threadIdx.x, w = blockIdx.x;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) h[lane + 64 * j] = 0;
-  __syncthreads();
-  const int64_t begin = (int64_t)w * per, end = begin + per < m ? begin + per : m;
-  for (int64_t i = begin + lane; i < end; i += 256) {  // 4 keys' loads in flight
-    uint64_t k[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) k[u] = i + 64 * u < end ? in[i + 64 * u] : 0ull;
-#pragma unroll
-    for (int u = 0; u < 4; ++u)
-      if (i + 64 * u < end) atomicAdd(&h[(uint32_t)(k[u] >> shift) & 255u], 1u);
-  }
-  __syncthreads();
-#pragma unroll
-  for (int j = 0; j < 4; ++j) hist[(int64_t)(lane + 64 * j) * W + w] = h[lane + 64 * j];
-}
-
-__device__ __forceinline__ uint32_t ce_wave_incl(uint32_t v, int lane) {
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const uint32_t o = __shfl_up(v, off, 64);
-    if (lane >= off) v += o;
-  }
-  return v;
-}
-
-// workgroup `bin`: hist[bin][0 .. W) -> its exclusive scan, totals[bin] = the sum
-__global__ __launch_bounds__(256) void ce_hist_scan(uint32_t* __restrict__ hist, int W, uint32_t* __restrict__ totals) {
-  __shared__ uint32_t wsum[4];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  uint32_t* row = hist + (int64_t)blockIdx.x * W;
-  const int ept = (W + 255) / 256;  // <= CE_WMAX / 256: a thread's entries stay in registers
-  const int i0 = tid * ept < W ? tid * ept : W, i1 = i0 + ept < W ? i0 + ept : W;
-  uint32_t v[CE_WMAX / 256], s = 0;
-#pragma unroll
-  for (int j = 0; j < CE_WMAX / 256; ++j) {
-    v[j] = i0 + j < i1 ? row[i0 + j] : 0u;
-    s += v[j];
-  }
-  const uint32_t incl = ce_wave_incl(s, lane);
-  if (lane == 63) wsum[wave] = incl;
-  __syncthreads();
-  uint32_t run = incl - s, total = 0;
-#pragma unroll
-  for (int w = 0; w < 4; ++w) {
-    if (w < wave) run += wsum[w];
-    total += wsum[w];
-  }
-#pragma unroll
-  for (int j = 0; j < CE_WMAX / 256; ++j) {
-    if (i0 + j < i1) row[i0 + j] = run;
-    run += v[j];
-  }
-  if (tid == 0) totals[blockIdx.x] = total;
-}
-
-__global__ __launch_bounds__(64) void ce_scatter(const uint64_t* __restrict__ in, uint64_t* __restrict__ out, int64_t m,
-                                                 int64_t per, int shift, const uint32_t* __restrict__ hist,
-                                                 const uint32_t* __restrict__ totals, int W) {
-  __shared__ uint32_t base[256];
-  const int lane = threadIdx.x, w = blockIdx.x;
-  {  // lane: digits 4 lane .. 4 lane + 3
-    uint32_t t[4], s = 0;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      t[j] = totals[4 * lane + j];
-      s += t[j];
-    }
-    uint32_t b = ce_wave_incl(s, lane) - s;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      base[4 * lane + j] = b + hist[(int64_t)(4 * lane + j) * W + w];
-      b += t[j];
-    }
-  }
-  __syncthreads();
-  const int64_t begin = (int64_t)w * per, end = begin + per < m ? begin + per : m;
-  const uint64_t below = (1ull << lane) - 1ull;
-  uint64_t ahead = begin + lane < end ? in[begin + lane] : 0ull;  // the next round's key, loaded a round early
-  for (int64_t i0 = begin; i0 < end; i0 += 64) {  // uniform trip count: the barriers are met by every lane
-    const int64_t i = i0 + lane;
-    const bool valid = i < end;
-    const uint64_t key = ahead;
-    ahead = i + 64 < end ? in[i + 64] : 0ull;
-    const uint32_t d = (uint32_t)(key >> shift) & 255u;
-    uint64_t same = __ballot(valid);
-#pragma unroll
-    for (int b = 0; b < 8; ++b) {
-      const bool bit = (d >> b) & 1u;
-      const uint64_t bal = __ballot(bit);
-      same &= bit ? bal : ~bal;
-    }
-    const uint32_t rank = __popcll(same & below), cnt = __popcll(same);
-    const uint32_t pos = valid ? base[d] : 0u;
-    __syncthreads();
-    if (valid && rank == 0) base[d] = pos + cnt;
-    __syncthreads();
-    if (valid && (int64_t)pos + rank < m) out[pos + rank] = key;
-  }
-}
+#include "radix_sort.h"
 
 // ------------------------------------------------------------------------------------------------ curve
 // the segmented-scan monoid: tp = labels, flag = a group starts, dtp / cnt = labels / keys since the last start
@@ -458,20 +354,17 @@ __global__ __launch_bounds__(1024) void ce_confusion_finish(const uint32_t* __re
 
 // ------------------------------------------------------------------------------------------------ host
 struct CeWork {
-  uint64_t *ka, *kb;
-  uint32_t *hist, *totals;
+  CeSort sort;
   CeAgg *tagg, *tpre;
   int32_t* segp;
   CePart* part;
   uint32_t* cpart;
-  int64_t per, tiles, bytes;
-  int W, cgrid;
+  int64_t tiles, bytes;
+  int cgrid;
 };
 inline CeWork ce_layout(int64_t n, int64_t c, void* work) {
   const int64_t m = n * c;
   CeWork w;
-  w.per = mmr::round_up(mmr::ceil_div(m, CE_WMAX), 64);
-  w.W = (int)mmr::ceil_div(m, w.per);
   const int64_t tc = c * mmr::ceil_div(n, CE_TILE), tm = mmr::ceil_div(m, CE_TILE);
   w.tiles = tc > tm ? tc : tm;
   char* p = (char*)work;
@@ -481,10 +374,7 @@ inline CeWork ce_layout(int64_t n, int64_t c, void* work) {
     off += mmr::round_up(bytes, 256);
     return at;
   };
-  w.ka = (uint64_t*)take(m * 8);
-  w.kb = (uint64_t*)take(m * 8);
-  w.hist = (uint32_t*)take((int64_t)256 * w.W * 4);
-  w.totals = (uint32_t*)take(256 * 4);
+  w.sort = ce_sort_layout(m, take);
   w.tagg = (CeAgg*)take(w.tiles * (int64_t)sizeof(CeAgg));
   w.tpre = (CeAgg*)take(w.tiles * (int64_t)sizeof(CeAgg));
   w.segp = (int32_t*)take(CE_MAXC * 4);
@@ -493,19 +383,6 @@ inline CeWork ce_layout(int64_t n, int64_t c, void* work) {
   w.cpart = (uint32_t*)take((int64_t)w.cgrid * 3 * 64 * 4);
   w.bytes = off;
   return w;
-}
-
-// ascending sort of keys[0 .. m) over bits [lo, hi); returns the array that holds the result (keys or alt)
-uint64_t* ce_sort(uint64_t* keys, uint64_t* alt, int64_t m, int lo, int hi, const CeWork& w, hipStream_t st) {
-  for (int shift = lo; shift < hi; shift += 8) {
-    ce_hist<<<dim3((unsigned)w.W), 64, 0, st>>>(keys, m, w.per, shift, w.hist, w.W);
-    ce_hist_scan<<<256, 256, 0, st>>>(w.hist, w.W, w.totals);
-    ce_scatter<<<dim3((unsigned)w.W), 64, 0, st>>>(keys, alt, m, w.per, shift, w.hist, w.totals, w.W);
-    uint64_t* t = keys;
-    keys = alt;
-    alt = t;
-  }
-  return keys;
 }
 
 // S segments of L sorted keys -> result rows row0 .. row0 + S - 1
@@ -549,13 +426,13 @@ mmr_status mmr_cls_eval(const float* scores, int64_t lds, const uint64_t* label_
   const CeWork w = ce_layout(n, c, work);
   MMR_CHECK_HIP(hipMemsetAsync(nonfinite, 0, sizeof(int64_t), st));
   const unsigned bgrid = (unsigned)(mmr::ceil_div(m, 256) < 2048 ? mmr::ceil_div(m, 256) : 2048);
-  ce_build_keys<<<bgrid, 256, 0, st>>>((const uint32_t*)scores, lds, label_bits, (uint32_t)c, (uint32_t)m, w.ka,
+  ce_build_keys<<<bgrid, 256, 0, st>>>((const uint32_t*)scores, lds, label_bits, (uint32_t)c, (uint32_t)m, w.sort.ka,
                                        (unsigned long long*)nonfinite);
   int cbits = 0;
   while ((1 << cbits) < c) ++cbits;
-  uint64_t* sm = ce_sort(w.ka, w.kb, m, 1, 33, w, st);  // by score: the micro segment
+  uint64_t* sm = ce_sort(w.sort.ka, w.sort.kb, m, 1, 33, w.sort, st);  // by score: the micro segment
   ce_curve(sm, 1, m, c, w, counts, ap_sum, best_thr, best_f1, st);
-  const uint64_t* sc = ce_sort(sm, sm == w.ka ? w.kb : w.ka, m, 33, 33 + cbits, w, st);  // stable: by class, then score
+  const uint64_t* sc = ce_sort(sm, sm == w.sort.ka ? w.sort.kb : w.sort.ka, m, 33, 33 + cbits, w.sort, st);  // stable: by class, then score
   ce_curve(sc, c, n, 0, w, counts, ap_sum, best_thr, best_f1, st);
   ce_confusion<<<dim3((unsigned)w.cgrid), 256, 0, st>>>((const uint32_t*)scores, lds, label_bits, n, c,
                                                         (const uint32_t*)(thresholds ? thresholds : best_thr), w.cpart);

@@ -294,7 +294,8 @@ class FusionStack:
             t.record_stream(main)
         return w["pq"], w["pp"], w["ev"], True
 
-    def forward(self, img_global, img_patches, txt_feats, patch_work=None, return_attention=False):
+    def forward(self, img_global, img_patches, txt_feats, patch_work=None, return_attention=False,
+                attention_layers=None):
         """img_global (B, Ci) f32, img_patches (B, Np, Ci) f32, txt_feats (B, L, Ct) bf16/f32 or None
         -> joint_emb (B, D) f32.  patch_work: this batch's patch_work(img_patches), started early by the
         caller (else it runs here).
@@ -304,6 +305,9 @@ class FusionStack:
         "layer_{i}_img2txt" (B, Np, L) (model.py:399-420; L = 1 for the default text token).  They come from
         extra launches (ops.mha_probs / x3_attention_probs) on the q / k rows the attention cores read; the
         value path runs the same launches on the same operands, so joint_emb has the same bits either way.
+        attention_layers: None (every layer, the reference's dictionary) or the layer indices whose maps are
+        wanted (negative: from the end) — the other layers' probability launches are not made and their keys are
+        absent; a layer's maps are the same bytes either way.
 
         Phase 1 (per layer, token level): enhancers, folded cross projections, the two cross
         attentions (means only where only means are used), patches_fused.
@@ -313,7 +317,7 @@ class FusionStack:
         nl*B*(Np+2) rows, its attention means and out-projection.
         Phase 4 (sequential): the joint chain (norm1 / alpha, norm2 -> FFN, adapter)."""
         if self.x3:
-            return self._forward_x3(img_global, img_patches, txt_feats, patch_work, return_attention)
+            return self._forward_x3(img_global, img_patches, txt_feats, patch_work, return_attention, attention_layers)
         B, Np, Ci = img_patches.shape
         D, h, eps, dev = self.D, self.heads, self.eps, self.device
         nl = len(self.layers)
@@ -325,6 +329,7 @@ class FusionStack:
         PF = torch.empty((nl, B * Np, D), dtype=torch.bfloat16, device=dev)
         cls = None
         attn = {} if return_attention else None
+        want = self._attention_layers(attention_layers) if return_attention else ()
         # the patch-side token work of every layer depends only on the image tower: it runs on a side
         # stream (or the caller's early patch_work), ahead of and concurrently with the text-side work,
         # which waits per layer on an event before the cross attentions (side_streams = False: one
@@ -353,7 +358,7 @@ class FusionStack:
             if two:
                 main.wait_event(ev[i])
             PQ, PP = pq[i], pp[i]
-            if attn is not None:  # on the main stream, after the wait: PQ is ready (and recorded on main)
+            if i in want:  # on the main stream, after the wait: PQ is ready (and recorded on main)
                 attn[f"layer_{i}_txt2img"] = ops.mha_probs(TQ[:, :D], PQ[:, :D], B, Lt, Np, h, dh, sc)
                 attn[f"layer_{i}_img2txt"] = ops.mha_probs(PQ[:, 2 * D:], TQ[:, D:2 * D], B, Np, Lt, h, dh, sc)
             ops.mha(TQ[:, :D], PQ[:, :D], PQ[:, D:2 * D], B, Lt, Np, h, dh, sc, mean_out=m1[i])
@@ -366,9 +371,10 @@ class FusionStack:
                 ops.mha(PQ[:, 2 * D:], TQ[:, D:2 * D], TQ[:, 2 * D:], B, Np, Lt, h, dh, sc, out=a2, mean_out=m2[i])
                 ops.linear(a2, L["o2_wb"], L["o2_b"], residual=PP, out=PF[i])  # patches_fused (fusion.py:437)
         del pq, pp
-        return self._finish(G, m1, m2, cls, PF, B, Np, Ci, attn)
+        return self._finish(G, m1, m2, cls, PF, B, Np, Ci, attn, want)
 
-    def _forward_x3(self, img_global, img_patches, txt_feats, patch_work=None, return_attention=False):
+    def _forward_x3(self, img_global, img_patches, txt_feats, patch_work=None, return_attention=False,
+                    attention_layers=None):
         """Phase 1 of forward in the fp32-faithful mode: f32 token rows, every GEMM and attention on
         bf16x3 (ops.x3_linear / ops.x3_attention).  As in the bf16 path, the patch-side work of every
         layer (enhancer, folded k/v/q + patch projections) runs on a side stream (or early, by the
@@ -387,6 +393,7 @@ class FusionStack:
         pq, pp, ev, two = self._patch_side(img_patches, patch_work)
         cls = torch.empty((nl, B, self.layers[0]["txt"].C), dtype=torch.float32, device=dev)
         attn = {} if return_attention else None
+        want = self._attention_layers(attention_layers) if return_attention else ()
         for i, L in enumerate(self.layers):
             PQ, PP = pq[i], pp[i]
             if txt_feats is None:  # learnable default text token (fusion.py:404-407)
@@ -400,7 +407,7 @@ class FusionStack:
             TQ = ops.x3_linear(Tes, L["t_x3"], L["t_b"]).reshape(B * Lt, -1)  # q_t2i | k_i2t | v_i2t
             if two:
                 main.wait_event(ev[i])
-            if attn is not None:
+            if i in want:
                 attn[f"layer_{i}_txt2img"] = ops.x3_attention_probs(TQ[:, :D], PQ[:, :D], B, Lt, Np, h, dh, sc)
                 attn[f"layer_{i}_img2txt"] = ops.x3_attention_probs(PQ[:, 2 * D:], TQ[:, D:2 * D], B, Np, Lt, h, dh, sc)
             ops.x3_attention(TQ[:, :D], PQ[:, :D], PQ[:, D:2 * D], B, Lt, Np, h, dh, sc, mean_out=m1[i])
@@ -408,11 +415,22 @@ class FusionStack:
                                         mean_out=m2[i])
             ops.x3_linear(a2, L["o2_x3t"], L["o2_b"], residual=PP, out=PF[i])  # patches_fused (fusion.py:437)
         del pq, pp
-        return self._finish(G, m1, m2, cls, PF, B, Np, Ci, attn)
+        return self._finish(G, m1, m2, cls, PF, B, Np, Ci, attn, want)
 
-    def _finish(self, G, m1, m2, cls, PF, B, Np, Ci, attn=None):
+    def _attention_layers(self, layers):
+        """forward's attention_layers -> the sorted layer indices whose maps are returned"""
+        nl = len(self.layers)
+        if layers is None:
+            return tuple(range(nl))
+        want = sorted({int(i) + nl if int(i) < 0 else int(i) for i in layers})
+        if want and not 0 <= want[0] <= want[-1] < nl:
+            raise ValueError(f"attention_layers {list(layers)} outside the {nl} fusion layers")
+        return tuple(want)
+
+    def _finish(self, G, m1, m2, cls, PF, B, Np, Ci, attn=None, want=()):
         """Phases 2-4 of forward (shared by the bf16 / fp8 and x3 modes).  attn: the cross-attention maps of
-        phase 1 (return_attention) — the combiner's maps are added and (joint, attn) returned."""
+        phase 1 (return_attention) for the layers `want` — the combiner's maps are added and (joint, attn)
+        returned."""
         D, h, eps, dev = self.D, self.heads, self.eps, self.device
         nl = len(self.layers)
         dh = D // h
@@ -442,9 +460,15 @@ class FusionStack:
             ops.mha(SQ[:, :D], SQ[:, D:2 * D], SQ[:, 2 * D:], nl * B, Np + 2, Np + 2, h, dh, sc, mean_out=m3)
         if attn is not None:  # rows [i B, (i + 1) B) of the launch over the nl*B sequences are layer i's
             probs = ops.x3_attention_probs if self.x3 else ops.mha_probs
-            comb = probs(SQ[:, :D], SQ[:, D:2 * D], nl * B, Np + 2, Np + 2, h, dh, sc)
-            attn = {f"layer_{i}_{k}": comb[i * B:(i + 1) * B] if k == "comb" else attn[f"layer_{i}_{k}"]
-                    for i in range(nl) for k in ("comb", "txt2img", "img2txt")}  # the reference's key order
+            if len(want) == nl:
+                comb = probs(SQ[:, :D], SQ[:, D:2 * D], nl * B, Np + 2, Np + 2, h, dh, sc)
+                comb = {i: comb[i * B:(i + 1) * B] for i in want}
+            else:  # a sequence's map does not depend on the rest of the launch: layer i's rows alone
+                r = B * (Np + 2)
+                comb = {i: probs(SQ[i * r:(i + 1) * r, :D], SQ[i * r:(i + 1) * r, D:2 * D], B, Np + 2, Np + 2, h, dh,
+                                 sc) for i in want}
+            attn = {f"layer_{i}_{k}": comb[i] if k == "comb" else attn[f"layer_{i}_{k}"]
+                    for i in want for k in ("comb", "txt2img", "img2txt")}  # the reference's key order
         fused = self._ql(m3, self.s_ow_x3, self.s_ob).view(nl, B, D)  # mean of self_attn output
         # phase 4: the joint chain
         joint = None

@@ -23,6 +23,8 @@ and micro aggregates) from the exact sums ops.cls_eval computes on the device.
 src/Evaluate/retrieval_diversity_compute.py:171-194 in f64 (the device computes them for whole batches of
 lists: GalleryIndex.list_diversity, the engines' diversity()); `diversity_summary` is one metric's row of
 its summary_all_metrics (:142-166).
+`compare_maps` is src/Helpers/helper.py:173-209 (Pearson, Spearman, top-k IoU of two heat maps) for device
+tensors, single maps or stacks of pairs, through ops.map_alignment (csrc/map_align.hip).
 """
 import math
 
@@ -339,3 +341,35 @@ def diversity_summary(values):
             "max": float(ok.max()) if cnt > 0 else nan,
             "count_nonnull": cnt, "total_rows": total,
             "pct_missing": 100.0 * (1.0 - cnt / total) if total > 0 else nan}
+
+
+def iou_key(topk_frac):
+    """compare_maps' IoU key (helper.py:208)"""
+    return f"iou_top{int(topk_frac * 100)}pct"
+
+
+def compare_maps(map_a, map_b, topk_frac=0.05):
+    """src/Helpers/helper.py:173-209 on the device: map_a, map_b (H, W) — or stacks (P, H, W) compared pair by
+    pair — float32 device tensors of equal shape -> {'pearson', 'spearman', f'iou_top{int(topk_frac*100)}pct'}:
+    floats for one pair, (P,) float64 numpy arrays for a stack.  Pearson and Spearman are 0.0 when either map is
+    constant (:188-190); iou = inter / (union + 1e-8) over the top max(1, int(HW * topk_frac)) pixels, ties
+    at the threshold included (np.partition's value, `>=`).  One ops.map_alignment call and one host sync; a
+    NaN / infinite pixel raises ValueError."""
+    from . import ops
+    a, b = torch.as_tensor(map_a), torch.as_tensor(map_b)
+    if a.shape != b.shape:
+        raise ValueError(f"compare_maps: shapes {tuple(a.shape)} and {tuple(b.shape)} differ")
+    single = a.dim() <= 2
+    if single:
+        a, b = a.reshape(1, -1), b.reshape(1, -1)
+    P = int(a.shape[0])
+    maps = torch.cat([a.reshape(P, -1), b.to(a.device).reshape(P, -1)]).to(torch.float32)
+    idx = torch.arange(P, dtype=torch.int64, device=maps.device)
+    r = ops.map_alignment(maps, idx, idx + P, fracs=(topk_frac,))
+    host = {k: r[k].cpu().numpy() for k in ("nonfinite", "inter_union", "pearson", "spearman")}  # the one sync
+    if int(host["nonfinite"][0]):
+        raise ValueError(f"compare_maps: {int(host['nonfinite'][0])} NaN / infinite pixels")
+    iu = host["inter_union"].astype(np.float64)
+    out = {"pearson": host["pearson"], "spearman": host["spearman"],
+           iou_key(topk_frac): iu[:, 0, 0] / (iu[:, 0, 1] + 1e-8)}
+    return {k: float(v[0]) for k, v in out.items()} if single else out

@@ -28,6 +28,7 @@ MultiModalRetrievalModel.predict(...) -> {"probs", "preds", "topk_idx", "topk_va
 """
 import collections
 import json
+import math
 import os
 from pathlib import Path
 
@@ -379,17 +380,25 @@ class MultiModalRetrievalModel:
         probability, equal probabilities by ascending class), "topk_vals": their probabilities (list of lists
         of float)}.  retrieve=True adds "retrieval_ids" / "retrieval_dists": per query what
         self.retriever.retrieve(joint_emb[i], K=K) returns (the loop of explain(), model.py:615-623).
-        explain=True — the reference's Integrated-Gradients / Grad-CAM maps — is not part of this
-        inference-only package."""
-        if explain:
+        explain="attention" (multimodal, needs a retriever) adds what the reference's explain=True adds, in its key
+        order: "retrieval_ids" / "retrieval_dists" as above, "attention_map" — ExplanationEngine.explain's
+        attention dictionary for query 0 (explain.py:825-947) as numpy float32 from explain_attention, keys in the
+        reference's order and left out / None where it does so: "txt2img" (H, W), "img2txt" (Lt,), "comb_img"
+        (H, W; left out when the vector is all zeros), "comb_txt", "final_patch_map", "final_token_map" — and
+        "ig_maps": None, "gradcam_maps": None.  explain=True — the reference's Integrated-Gradients / Grad-CAM
+        maps — is not part of this inference-only package."""
+        attention = isinstance(explain, str) and explain == "attention"
+        if explain and not attention:
             raise NotImplementedError(
                 "predict(explain=True): the reference's IG / Grad-CAM explanations need autograd and Captum and are "
-                "out of scope here; use forward(..., return_attention=True) for the attention maps and "
+                "out of scope here; use predict(..., explain=\"attention\") for the attention heat maps "
+                "(explain_attention for whole batches), forward(..., return_attention=True) for the raw maps and "
                 "predict(..., retrieve=True) for the retrieved neighbours")
         if self.classifier is None:
             raise ValueError("predict needs classifier.0.* / classifier.3.* weights in the checkpoint / head_state")
-        if retrieve and self.retriever is None:
-            raise ValueError("predict(retrieve=True) needs a retriever (set_retriever / retriever=)")
+        if (retrieve or attention) and self.retriever is None:
+            raise ValueError("predict(retrieve=True / explain=\"attention\") needs a retriever (set_retriever / "
+                             "retriever=)")
         thr_vec = None
         if isinstance(threshold, (torch.Tensor, np.ndarray, list, tuple)) and np.ndim(threshold) > 0:
             # per-class thresholds (the reference's `probs >= threshold` broadcasts, e.g. best_ts of
@@ -398,7 +407,12 @@ class MultiModalRetrievalModel:
             if tuple(thr_vec.shape) != (self.classifier.c,):
                 raise ValueError(f"predict: threshold must be a scalar or have shape ({self.classifier.c},), got "
                                  f"{tuple(thr_vec.shape)}")
-        joint = self._forward(image, input_ids, attention_mask)["joint_emb"]
+        expl = None
+        if attention:  # the same forward, with the last layer's maps
+            expl = self.explain_attention(image, input_ids, attention_mask)
+            joint = expl["joint_emb"]
+        else:
+            joint = self._forward(image, input_ids, attention_mask)["joint_emb"]
         if thr_vec is None:
             res = ops.classifier_head(joint, self.classifier, k=K, threshold=threshold,
                                       want=("probs", "preds", "topk_vals", "topk_idx"))
@@ -407,14 +421,130 @@ class MultiModalRetrievalModel:
             res["preds"] = (res["probs"] >= thr_vec[None, :]).to(torch.int32)
         output = {"probs": res["probs"].cpu().numpy(), "preds": res["preds"].cpu().numpy(),
                   "topk_idx": res["topk_idx"].cpu().tolist(), "topk_vals": res["topk_vals"].cpu().tolist()}
-        if retrieve:
+        if retrieve or attention:
             ids, dists = [], []
             for q in joint.detach().cpu().numpy():
                 i, d = self.retriever.retrieve(q, K=K)
                 ids.append(i)
                 dists.append(d)
             output["retrieval_ids"], output["retrieval_dists"] = ids, dists
+        if attention:
+            def first(k):
+                return None if expl[k] is None else expl[k][0].cpu().numpy()
+            amap = {}
+            if expl["txt2img"] is not None:
+                amap["txt2img"] = first("txt2img")
+            amap["img2txt"] = first("img2txt")
+            if expl["comb_img"] is not None and bool(expl["comb_img_valid"][0]):
+                amap["comb_img"] = first("comb_img")
+            amap["comb_txt"] = first("comb_txt")
+            amap["final_patch_map"] = first("final_patch_map")
+            amap["final_token_map"] = first("final_token_map")
+            output.update({"attention_map": amap, "ig_maps": None, "gradcam_maps": None})
         return output
+
+    def explain_attention(self, image, input_ids, attention_mask, layer=-1, image_size=(224, 224)):
+        """The attention family of ExplanationEngine.explain (explain.py:825-947) for every sample of the batch
+        (the reference explains sample 0 only): one forward with the maps of fusion layer `layer` left on the
+        device (the other layers' probability launches are not made) and one ops.explain_attention call ->
+        batched device tensors "txt2img" (B, H, W), "img2txt" (B, Lt), "comb_img" (B, H, W), "comb_txt"
+        (B, min(T, Np + 2)), "final_patch_map" (B, H, W), "final_token_map", plus "comb_img_valid" (B,) bool
+        (False: the reference leaves that sample's comb_img out, :865) and "joint_emb" (B, D).  input_ids=None:
+        the default text token (Lt = T = 1).  The heat maps are None when Np is not a perfect square (:834-836).
+        Deviation: steps 3-5 of compute_comb_token_vector (:572-640) run only for a comb_txt that is all
+        <= 1e-7, which a row-stochastic map cannot give; such a sample raises ValueError instead."""
+        if self.model_type != "multimodal":
+            raise ValueError(f"explain_attention needs model_type='multimodal' (the fusion layers' attention maps), "
+                             f"not {self.model_type!r}")
+        if image is None:
+            raise ValueError("model_type='multimodal' needs an image (fusion.py:421)")
+        nl = len(self.fusion.layers)
+        li = int(layer) + nl if int(layer) < 0 else int(layer)
+        if not 0 <= li < nl:
+            raise ValueError(f"explain_attention: layer {layer} outside the {nl} fusion layers")
+        img_global, patches, _ = self.backbones.encode_image(image, want_patches=True)
+        txt = self.backbones.encode_text(input_ids, attention_mask) if input_ids is not None else None
+        joint, maps = self.fusion.forward(img_global, patches, txt, return_attention=True, attention_layers=[li])
+        t2i = maps[f"layer_{li}_txt2img"]
+        npatch = int(t2i.shape[2])
+        square = math.isqrt(npatch) ** 2 == npatch
+        r = ops.explain_attention(t2i, maps[f"layer_{li}_img2txt"], maps[f"layer_{li}_comb"],
+                                  text_len=int(txt.shape[1]) if txt is not None else 1,
+                                  image_size=image_size if square else None)
+        flags = torch.cat([r["nonfinite"].to(torch.float32), r["comb_absmax"].reshape(-1)]).cpu().numpy()
+        if flags[0]:
+            raise ValueError(f"explain_attention: {int(flags[0])} NaN / infinite entries in the attention vectors")
+        absmax = flags[1:].reshape(-1, 2)
+        dead = np.nonzero(absmax[:, 1] <= 1e-7)[0]
+        if dead.size:
+            raise ValueError(f"explain_attention: comb_txt of sample {int(dead[0])} is all <= 1e-7; the reference's "
+                             f"fallback cascade (explain.py:572-640) is not built")
+        return {"txt2img": r["map_txt2img"], "img2txt": r["t_img"], "comb_img": r["map_comb"], "comb_txt": r["t_comb"],
+                "final_patch_map": r["map_final"], "final_token_map": r["final_token"],
+                "comb_img_valid": r["comb_absmax"][:, 0] > 1e-8, "joint_emb": joint}
+
+    def evaluate_explanations(self, batches, K=10, fracs=(0.05, 0.20), image_size=(224, 224), exclude_self=False,
+                              return_per_query=False):
+        """The loop of src/Evaluate/retrieval_explain_eval.py:173-266 (explainability alignment, test -> test):
+        `batches` yields (image, input_ids, attention_mask); concatenated in order they are the retriever's gallery.
+        Per batch explain_attention's final_patch_map and joint_emb stay on the device; then ONE batched top-K
+        (search for the exact engine, retrieve_batch for DLS), the neighbour = list position 0 (exclude_self: the
+        first index that is not the query's own), and ONE ops.map_alignment call over the (query, neighbour) pairs
+        -> {"pearson_mean", "spearman_mean", "iou05_mean", "iou20_mean" (one "iouNN_mean" per fraction), "n_pairs"};
+        return_per_query adds "pearson", "spearman", "iouNN" (n_pairs,) float64 and "query_index" / "neighbor_index".
+        Means are 0.0 with no pairs; queries whose list is empty are skipped.  Deliberate difference: the
+        reference compares the batch's sample-0 map for every query of the batch (:192, 211); this compares each
+        query's own map."""
+        if self.retriever is None:
+            raise ValueError("evaluate_explanations needs a retriever (set_retriever / retriever=)")
+
+        def dev(t):
+            return t.to(self.device) if isinstance(t, torch.Tensor) else t
+        maps, embs = [], []
+        for image, input_ids, attention_mask in batches:
+            e = self.explain_attention(dev(image), dev(input_ids), dev(attention_mask), image_size=image_size)
+            if e["final_patch_map"] is None:
+                raise ValueError("evaluate_explanations: the patch count is not a perfect square (no heat maps)")
+            maps.append(e["final_patch_map"])
+            embs.append(e["joint_emb"])
+        names = [f"iou{int(round(f * 100)):02d}" for f in fracs]
+        out = {"pearson_mean": 0.0, "spearman_mean": 0.0, **{n + "_mean": 0.0 for n in names}, "n_pairs": 0}
+        per = {"pearson": np.zeros(0), "spearman": np.zeros(0), **{n: np.zeros(0) for n in names},
+               "query_index": np.zeros(0, np.int64), "neighbor_index": np.zeros(0, np.int64)}
+        if maps:
+            maps, embs = torch.cat(maps), torch.cat(embs)
+            n = int(maps.shape[0])
+            if n != len(self.retriever.ids):
+                raise ValueError(f"evaluate_explanations: {n} queries but the retriever's gallery has "
+                                 f"{len(self.retriever.ids)} rows (test -> test: the batches are the gallery)")
+            kk = int(K) + (1 if exclude_self else 0)
+            if hasattr(self.retriever, "retrieve_batch"):
+                idx = self.retriever.retrieve_batch(embs, K=kk)[0]
+            else:
+                idx = self.retriever.search(embs, K=kk)[0]
+            idx = idx.to(maps.device)
+            own = torch.arange(n, dtype=torch.int64, device=maps.device)
+            ok = idx >= 0
+            if exclude_self:
+                ok &= idx != own[:, None]
+            has = ok.any(1) if idx.shape[1] else torch.zeros(n, dtype=torch.bool, device=maps.device)
+            pos = ok.to(torch.int8).argmax(1) if idx.shape[1] else own
+            nb = idx.gather(1, pos[:, None])[:, 0] if idx.shape[1] else own
+            qa, qb = own[has], nb[has]
+            if int(qa.shape[0]):
+                r = ops.map_alignment(maps, qa, qb, fracs=fracs)
+                bad = int(r["nonfinite"].item())
+                if bad:
+                    raise ValueError(f"evaluate_explanations: {bad} NaN / infinite map pixels")
+                iu = r["inter_union"].cpu().numpy().astype(np.float64)
+                per = {"pearson": r["pearson"].cpu().numpy(), "spearman": r["spearman"].cpu().numpy(),
+                       **{nm: iu[:, j, 0] / (iu[:, j, 1] + 1e-8) for j, nm in enumerate(names)},
+                       "query_index": qa.cpu().numpy(), "neighbor_index": qb.cpu().numpy()}
+                out = {"pearson_mean": float(per["pearson"].mean()), "spearman_mean": float(per["spearman"].mean()),
+                       **{nm + "_mean": float(per[nm].mean()) for nm in names}, "n_pairs": int(qa.shape[0])}
+        if return_per_query:
+            out.update(per)
+        return out
 
     def evaluate_classifier(self, batches, thresholds=None, return_outputs=False):
         """eval_on_test (src/Evaluate/eval_on_test.py:103-207) over `batches`, an iterable of (image, input_ids,

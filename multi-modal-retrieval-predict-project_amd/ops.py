@@ -603,6 +603,158 @@ def cls_eval(scores, label_bits, num_classes, thresholds=None):
     return res
 
 
+EXPLAIN_MAX_PATCHES, EXPLAIN_MAX_LEN, MAP_MAX_PIXELS = 1024, 4096, 65536
+
+
+def _rows3(t, name):
+    """(B, R, C) f32 device tensor with unit column stride -> (tensor, batch stride, row stride)"""
+    if t.dim() != 3 or t.dtype != torch.float32:
+        raise ValueError(f"explain_attention: {name} must be (B, rows, cols) float32, got {tuple(t.shape)} {t.dtype}")
+    if t.shape[2] > 1 and t.stride(2) != 1:
+        t = t.contiguous()
+    B, R, C = t.shape
+    rs = t.stride(1) if R > 1 else C
+    bs = t.stride(0) if B > 1 else R * rs
+    if rs < C:  # expanded rows
+        t = t.contiguous()
+        rs, bs = C, R * C
+    return t, bs, rs
+
+
+def explain_attention(txt2img=None, img2txt=None, comb=None, text_len=None, image_size=None):
+    """The attention explanations of a batch in one mmr_explain_attention call (csrc/explain.hip; the reference's
+    ExplanationEngine.explain, explain.py:825-947): txt2img (B, Lt, Np), img2txt (B, Np, Lt), comb (B, Lc, Lc) f32
+    device maps (each may be None; rows at unit stride, any batch / row stride), text_len = txt_feats.shape[1]
+    (default Lt), image_size (H, W) or None (no heat maps).  -> dict of device tensors (None where the reference
+    has no such vector): p_txt (B, Np), t_img (B, Lt), p_comb (B, Np), t_comb (B, min(T, Lc)), final_patch
+    (B, Np), final_token, the heat maps map_txt2img / map_comb / map_final (B, H, W), offsets (B, 2) int32 (the
+    chosen column / row window), comb_absmax (B, 2) = max |p_comb|, max |t_comb|, nonfinite (1,) int64.  Nothing
+    is synchronised."""
+    given = [t for t in (txt2img, img2txt, comb) if t is not None]
+    if not given:
+        raise ValueError("explain_attention: no attention map given")
+    _lib.require_gpu(given[0])
+    dev = given[0].device
+    B = int(given[0].shape[0])
+    bs = {}
+    lt = npp = None
+    if txt2img is not None:
+        txt2img, bs["t2i"], rs_t2i = _rows3(txt2img, "txt2img")
+        lt, npp = int(txt2img.shape[1]), int(txt2img.shape[2])
+    if img2txt is not None:
+        img2txt, bs["i2t"], rs_i2t = _rows3(img2txt, "img2txt")
+        if lt is not None and (int(img2txt.shape[1]), int(img2txt.shape[2])) != (npp, lt):
+            raise ValueError(f"explain_attention: img2txt {tuple(img2txt.shape)} does not match txt2img "
+                             f"{tuple(txt2img.shape)}")
+        npp, lt = int(img2txt.shape[1]), int(img2txt.shape[2])
+    lcr = lcc = 0
+    if comb is not None:
+        comb, bs["comb"], rs_comb = _rows3(comb, "comb")
+        lcr, lcc = int(comb.shape[1]), int(comb.shape[2])
+    if any(int(t.shape[0]) != B for t in given):
+        raise ValueError("explain_attention: the maps' batch sizes differ")
+    if npp is None:
+        raise ValueError("explain_attention: comb alone does not give the patch count; pass txt2img or img2txt")
+    T = int(text_len) if text_len is not None else lt
+    H, W = (int(image_size[0]), int(image_size[1])) if image_size is not None else (0, 0)
+    lc = lcr if comb is not None else 0
+    has_pc = comb is not None and lc >= npp
+    ltc = min(T, lc)
+    lft = min(lt, ltc) if (img2txt is not None and comb is not None) else (lt if img2txt is not None else ltc)
+
+    def f32(*shape):
+        return torch.empty(shape, dtype=torch.float32, device=dev)
+    heat = image_size is not None
+    r = {"p_txt": f32(B, npp) if txt2img is not None else None,
+         "t_img": f32(B, lt) if img2txt is not None else None,
+         "p_comb": f32(B, npp) if has_pc else None,
+         "t_comb": f32(B, ltc) if comb is not None else None,
+         "final_patch": f32(B, npp) if (txt2img is not None or has_pc) else None,
+         "final_token": f32(B, lft) if (img2txt is not None or comb is not None) else None,
+         "map_txt2img": f32(B, H, W) if heat and txt2img is not None else None,
+         "map_comb": f32(B, H, W) if heat and has_pc else None,
+         "map_final": f32(B, H, W) if heat and (txt2img is not None or has_pc) else None,
+         "offsets": torch.empty((B, 2), dtype=torch.int32, device=dev),
+         "comb_absmax": f32(B, 2) if comb is not None else None,
+         "nonfinite": torch.empty((1,), dtype=torch.int64, device=dev)}
+    work = None
+    if comb is not None:
+        nwork = int(_L().mmr_explain_attention_work_bytes(B, lt, npp, lc))
+        if nwork <= 0:
+            raise ValueError(f"explain_attention: shape B = {B}, Lt = {lt}, Np = {npp}, Lc = {lc} is not taken "
+                             f"(Np <= {EXPLAIN_MAX_PATCHES}, Lt, Lc <= {EXPLAIN_MAX_LEN})")
+        work = torch.empty(nwork, dtype=torch.uint8, device=dev)
+    _chk(_L().mmr_explain_attention(
+        _lib.ptr(txt2img), bs.get("t2i", 0), rs_t2i if txt2img is not None else 0,
+        _lib.ptr(img2txt), bs.get("i2t", 0), rs_i2t if img2txt is not None else 0,
+        _lib.ptr(comb), bs.get("comb", 0), rs_comb if comb is not None else 0,
+        B, lt, npp, lcr, lcc, T, H, W, _lib.ptr(r["p_txt"]), _lib.ptr(r["t_img"]), _lib.ptr(r["p_comb"]),
+        _lib.ptr(r["t_comb"]), _lib.ptr(r["final_patch"]), _lib.ptr(r["final_token"]), _lib.ptr(r["map_txt2img"]),
+        _lib.ptr(r["map_comb"]), _lib.ptr(r["map_final"]), _lib.ptr(r["offsets"]), _lib.ptr(r["comb_absmax"]),
+        _lib.ptr(r["nonfinite"]), _lib.ptr(work), _s(given[0])), "mmr_explain_attention")
+    return r
+
+
+def topk_count(n, frac):
+    """compare_maps' k (helper.py:198): max(1, int(n * frac))"""
+    return max(1, int(n * frac))
+
+
+def map_alignment(maps, pa, pb, fracs=(0.05, 0.20)):
+    """compare_maps (src/Helpers/helper.py:173-209) for P pairs in one mmr_map_alignment call (csrc/map_align.hip):
+    maps (N, HW) or (N, H, W) f32 device (unit pixel stride), pa / pb (P,) int64 map indices (entries outside [0, N)
+    are skipped and flagged), fracs: at most 4 top-k fractions, k = max(1, int(HW * frac)).  -> dict of device
+    tensors: pearson, spearman (P,) f64 (0.0 where either map is constant), inter_union (P, F, 2) int64 (iou =
+    inter / (union + 1e-8)), rank_sums (P, 3) int64 = S_ab, S_aa, S_bb of the centred doubled ranks, skipped (P,)
+    int32; per map ranks2 (N, HW) int32 (2 x the average rank; the C ABI's uint32), thresholds (N, F) f32,
+    constant (N,) int32, mean, ssd (N,) f64; nonfinite (1,) int64 and k (the list of k).  Nothing is
+    synchronised: a NaN / infinite pixel shows in `nonfinite` (the other outputs are then undefined)."""
+    _lib.require_gpu(maps)
+    if maps.dim() == 3:
+        maps = maps.reshape(maps.shape[0], -1)
+    if maps.dim() != 2 or maps.dtype != torch.float32:
+        raise ValueError(f"map_alignment: maps must be (N, HW) or (N, H, W) float32, got {tuple(maps.shape)} "
+                         f"{maps.dtype}")
+    N, HW = (int(x) for x in maps.shape)
+    if not 1 <= N <= MAP_MAX_PIXELS or not 1 <= HW <= MAP_MAX_PIXELS or N * HW >= 2 ** 31:
+        raise ValueError(f"map_alignment: N = {N}, HW = {HW} outside 1..{MAP_MAX_PIXELS} each / N * HW < 2^31")
+    if (HW > 1 and maps.stride(1) != 1) or (N > 1 and maps.stride(0) < HW):
+        maps = maps.contiguous()
+    ld = maps.stride(0) if N > 1 else HW
+    fracs = tuple(float(f) for f in fracs)
+    if len(fracs) > 4:
+        raise ValueError(f"map_alignment: {len(fracs)} fractions, at most 4")
+    ks = [topk_count(HW, f) for f in fracs]
+    if any(not 1 <= k <= HW for k in ks):
+        raise ValueError(f"map_alignment: fractions {fracs} give k = {ks} outside 1..{HW}")
+    dev = maps.device
+    pa = torch.as_tensor(pa, dtype=torch.int64).to(dev).contiguous().view(-1)
+    pb = torch.as_tensor(pb, dtype=torch.int64).to(dev).contiguous().view(-1)
+    if pa.shape != pb.shape:
+        raise ValueError(f"map_alignment: {pa.shape[0]} / {pb.shape[0]} pair entries")
+    P, F = int(pa.shape[0]), len(ks)
+
+    def out(shape, dt):
+        return torch.empty(shape, dtype=dt, device=dev)
+    r = {"ranks2": out((N, HW), torch.int32), "thresholds": out((N, F), torch.float32),
+         "constant": out((N,), torch.int32), "mean": out((N,), torch.float64), "ssd": out((N,), torch.float64),
+         "pearson": out((P,), torch.float64), "spearman": out((P,), torch.float64),
+         "rank_sums": out((P, 3), torch.int64), "inter_union": out((P, F, 2), torch.int64),
+         "skipped": out((P,), torch.int32), "nonfinite": out((1,), torch.int64), "k": ks}
+    nwork = int(_L().mmr_map_alignment_work_bytes(N, HW))
+    if nwork <= 0:
+        raise ValueError(f"map_alignment: shape ({N}, {HW}) is not taken")
+    work = torch.empty(nwork, dtype=torch.uint8, device=dev)
+    kk = ks + [1] * (4 - F)
+    _chk(_L().mmr_map_alignment(_lib.ptr(maps), ld, N, HW, _lib.ptr(pa), _lib.ptr(pb), P, F, *kk,
+                                _lib.ptr(r["ranks2"]), _lib.ptr(r["thresholds"]), _lib.ptr(r["constant"]),
+                                _lib.ptr(r["mean"]), _lib.ptr(r["ssd"]), _lib.ptr(r["pearson"]),
+                                _lib.ptr(r["spearman"]), _lib.ptr(r["rank_sums"]), _lib.ptr(r["inter_union"]),
+                                _lib.ptr(r["skipped"]), _lib.ptr(r["nonfinite"]), _lib.ptr(work), _s(maps)),
+         "mmr_map_alignment")
+    return r
+
+
 def mha(q, k, v, b, lq, lk, heads, dh, scale, out=None, mean_out=None, q8=False):
     """Attention core over strided row views: q (b*lq, >=heads*dh) etc. (unit column stride).  q8: the
     output also as an MX-fp8 activation operand, returned as (out, mean_out, MXFP8)."""
