@@ -308,6 +308,29 @@ int32_t mmr_linear_bf16_ln_parts(int64_t m, int32_t n, int32_t ln_mode);
 /* Number of launch variants mmr_linear_bf16 chooses among (indices 0 .. n-1 of its table). */
 int32_t mmr_linear_bf16_n_variants(void);
 
+/* The kernels mmr_linear_bf16 launches (its routes).  A variant names a wish; the shape guards decide (DESIGN.md,
+ * "Routes of the bf16 tiled GEMM"): a variant whose guards fail falls through to a later route, at last to BASE.
+ * Residual rounding: the BASE and BIG routes round act(acc + bias) to bf16 and round again after adding the bf16
+ * residual (two roundings); the P8 routes add the residual in f32 and round once; the W4 routes take no residual. */
+enum {
+  MMR_GEMM_ROUTE_BASE_128X128 = 0,       /* gemm_bf16_tn: 4 waves, any m; n, k multiples of 8 */
+  MMR_GEMM_ROUTE_W4_256X256 = 1,         /* gemm_bf16_tn_w4<8>: persistent, 4 waves, no residual */
+  MMR_GEMM_ROUTE_W4_256X192 = 2,         /* gemm_bf16_tn_w4<6> */
+  MMR_GEMM_ROUTE_BIG_256X256_KB64X2 = 3, /* gemm_bf16_tn_big, 8 waves: tile, K slice depth x LDS stages */
+  MMR_GEMM_ROUTE_BIG_256X256_KB32X4 = 4,
+  MMR_GEMM_ROUTE_BIG_256X192_KB64X2 = 5,
+  MMR_GEMM_ROUTE_BIG_256X128_KB32X2 = 6,
+  MMR_GEMM_ROUTE_BIG_256X128_KB32X3 = 7,
+  MMR_GEMM_ROUTE_BIG_256X128_KB64X3 = 8,
+  MMR_GEMM_ROUTE_P8_256X256 = 9,         /* gemm_bf16_tn_p8<4>: persistent 8-phase, 8 waves */
+  MMR_GEMM_ROUTE_P8_256X192 = 10,        /* gemm_bf16_tn_p8<3> */
+  MMR_GEMM_N_ROUTES = 11
+};
+/* The kernel mmr_linear_bf16 launches for (m, n, k, has_residual) under `variant` on a device with `cus`
+   compute units (cus <= 0: the current device).  Launches nothing.  -1: bad arguments (what mmr_linear_bf16
+   refuses, m = 0, or a variant outside 0 .. mmr_linear_bf16_n_variants() - 1). */
+int32_t mmr_linear_bf16_route(int64_t m, int32_t n, int32_t k, int32_t has_residual, int32_t variant, int32_t cus);
+
 /* Test / A-B hook (the product path never calls it): pin a launch variant for the whole process.
  *   MMR_PIN_GEMM_BF16: value = mmr_linear_bf16 variant index, or -1 = per-shape tuning (default);
  *   MMR_PIN_X3_WAVES:  value = 4 or 8 waves per mmr_linear_x3 tile (8 only where K % 256 == 0),

@@ -47,6 +47,7 @@ SIGNATURES = {
     "mmr_linear_bf16": [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i32, c_i32, c_i32, c_vp],
     "mmr_linear_bf16_variant": [c_i64, c_i32, c_i32, c_i32, c_i32, c_i32],
     "mmr_linear_bf16_n_variants": [],
+    "mmr_linear_bf16_route": [c_i64, c_i32, c_i32, c_i32, c_i32, c_i32],
     "mmr_linear_bf16_ln_parts": [c_i64, c_i32, c_i32],
     "mmr_linear_bf16_ln": [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp,
                            c_vp],
@@ -153,6 +154,7 @@ SIGNATURES = {
 }
 _RESTYPES = {"mmr_last_error": ctypes.c_char_p, "mmr_version": ctypes.c_int, "mmr_max_k": ctypes.c_int,
              "mmr_linear_bf16_variant": ctypes.c_int32, "mmr_linear_bf16_n_variants": ctypes.c_int32,
+             "mmr_linear_bf16_route": ctypes.c_int32,
              "mmr_linear_bf16_ln_parts": ctypes.c_int32,
              "mmr_linear_rw_parts": ctypes.c_int32,
              "mmr_swin_mlp_pack_elems": ctypes.c_int64, "mmr_swin_attn_block_pack_bytes": ctypes.c_int64,

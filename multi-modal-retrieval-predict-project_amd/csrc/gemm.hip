@@ -1817,74 +1817,93 @@ constexpr int kVariants = 11;
 constexpr int kVarW4[kVariants] = {1, 2, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 constexpr int kVarCfg[kVariants] = {1, 1, 1, 2, 3, 4, 5, 6, 0, 7, 8};
 
-template <int ACT, bool HB, bool HR>
-void launch(const uint16_t* x, const uint16_t* w, const float* b, const uint16_t* r, uint16_t* y,
-            int64_t m, int n, int k, hipStream_t st, int w4, int cfg) {
+// The kernel a (w4, cfg) pair launches for a shape on a device with `cus` compute units (MMR_GEMM_ROUTE_* of
+// mmr.h): the one definition of the guards; launch() switches over it and mmr_linear_bf16_route reports it.
+int route(int64_t m, int n, int k, bool hr, int w4, int cfg, int cus) {
   // big tiles when the grid still fills >= ~2 rounds of 256 CUs and K is deep enough
   const int64_t t256 = mmr::ceil_div(m, 256);
   // the persistent 4-wave kernel for epilogues without a residual (its 1-wave-per-SIMD epilogue
-  // cannot hide a residual tile's fetch); residual GEMMs keep the 8-wave kernels
-  if (w4 && !HR && k >= 256 && k % 64 == 0 && m >= 4096) {
+  // cannot hide a residual tile's fetch; 128x128 wave tiles: no registers left for a residual tile);
+  // residual GEMMs keep the 8-wave kernels
+  if (w4 && !hr && k >= 256 && k % 64 == 0 && m >= 4096) {
     // persistent grid: a multiple of 8 workgroups (one per CU), tiles split evenly per XCD
-    const int grid = std::max(8, cu_count() / 8 * 8);
-    if constexpr (!HR) {  // 128x128 wave tiles: no registers left for a residual tile
-      if (w4 == 1 && n % 256 == 0 && (t256 * (n / 256)) % grid == 0) {
-        const int tm = (int)t256, tn = n / 256;
+    const int grid = std::max(8, cus / 8 * 8);
+    if (w4 == 1 && n % 256 == 0 && (t256 * (n / 256)) % grid == 0) return MMR_GEMM_ROUTE_W4_256X256;
+    if (n % 192 == 0) return MMR_GEMM_ROUTE_W4_256X192;
+  }
+  if (cfg >= 7 && k % 128 == 0 && m % 256 == 0) {  // persistent 8-phase: 7 -> 256x256, 8 -> 256x192
+    if (cfg == 7 && n % 256 == 0) return MMR_GEMM_ROUTE_P8_256X256;
+    if (cfg == 8 && n % 192 == 0) return MMR_GEMM_ROUTE_P8_256X192;
+  }
+  if (cfg != 0 && k >= 256 && m >= 4096) {
+    if (cfg <= 2 && n % 256 == 0 && t256 * (n / 256) >= 512)
+      return cfg == 1 ? MMR_GEMM_ROUTE_BIG_256X256_KB64X2 : MMR_GEMM_ROUTE_BIG_256X256_KB32X4;
+    if (cfg == 6 && n % 192 == 0 && t256 * (n / 192) >= 256) return MMR_GEMM_ROUTE_BIG_256X192_KB64X2;
+    // 256x128, KB=32: 2 workgroups per CU (epilogue overlap)
+    if (cfg >= 4 && cfg <= 5 && n % 128 == 0)
+      return cfg == 4 ? MMR_GEMM_ROUTE_BIG_256X128_KB32X2 : MMR_GEMM_ROUTE_BIG_256X128_KB32X3;
+    if (n % 128 == 0 && t256 * (n / 128) >= 512) return MMR_GEMM_ROUTE_BIG_256X128_KB64X3;
+  }
+  return MMR_GEMM_ROUTE_BASE_128X128;
+}
+
+// The one launch of gemm_bf16_tn_big: one workgroup per (WM MT 16) x (WN NT 16) tile, KB-deep slices through a
+// STAGES-deep LDS ring (or the epilogue staging, whichever is larger); OCC = 2: two workgroups per CU
+struct BigArgs {
+  const uint16_t* x;
+  const uint16_t* w;
+  const float* b;
+  const uint16_t* r;
+  uint16_t* y;
+  int64_t m;
+  int n, k;
+};
+template <int WM, int WN, int MT, int NT, int KB, int STAGES, int OCC, int ACT, bool HB, bool HR>
+void launch_big(const BigArgs& a, hipStream_t st) {
+  constexpr int TBM = WM * MT * 16, TBN = WN * NT * 16;
+  const int tm = (int)mmr::ceil_div(a.m, TBM), tn = a.n / TBN;
+  const size_t lds = std::max<size_t>(STAGES * (TBM + TBN) * KB * 2, EPI_BIG_B);
+  gemm_bf16_tn_big<WM, WN, MT, NT, KB, STAGES, ACT, HB, HR, OCC>
+      <<<dim3(tm * tn), dim3(512), lds, st>>>(a.x, a.w, a.b, a.r, a.y, a.m, a.n, a.k, tm, tn);
+}
+
+template <int ACT, bool HB, bool HR>
+void launch(const uint16_t* x, const uint16_t* w, const float* b, const uint16_t* r, uint16_t* y,
+            int64_t m, int n, int k, hipStream_t st, int w4, int cfg) {
+  const int tm = (int)mmr::ceil_div(m, 256);  // row tiles of the persistent routes
+  const BigArgs ba{x, w, b, r, y, m, n, k};
+  switch (route(m, n, k, HR, w4, cfg, cu_count())) {
+    case MMR_GEMM_ROUTE_W4_256X256:
+      if constexpr (!HR) {  // (the route takes no residual)
+        // persistent grid: a multiple of 8 workgroups (one per CU), tiles split evenly per XCD
+        const int grid = std::max(8, cu_count() / 8 * 8), tn = n / 256;
         gemm_bf16_tn_w4<8, ACT, HB, HR><<<dim3(std::min<int64_t>(grid, (int64_t)tm * tn)), dim3(256), w4_lds_bytes<8>(), st>>>(x, w, b, r, y, m, n, k, tm, tn);
-        return;
       }
-    }
-    if (n % 192 == 0) {
-      const int tm = (int)t256, tn = n / 192;
+      return;
+    case MMR_GEMM_ROUTE_W4_256X192: {
+      const int grid = std::max(8, cu_count() / 8 * 8), tn = n / 192;
       gemm_bf16_tn_w4<6, ACT, HB, HR><<<dim3(std::min<int64_t>(grid, (int64_t)tm * tn)), dim3(256), w4_lds_bytes<6>(), st>>>(x, w, b, r, y, m, n, k, tm, tn);
       return;
     }
-  }
-  if (cfg >= 7 && k % 128 == 0 && m % 256 == 0) {  // persistent 8-phase: 7 -> 256x256, 8 -> 256x192
-    P8Args a;
-    a.x = x, a.w = w, a.bias = b, a.r = r, a.y = y, a.m = m, a.n = n, a.k = k;
-    a.ntst = p8_nt(m, n, 2);
-    if (cfg == 7 && n % 256 == 0) return launch_p8<4, ACT, HB, HR>(a, st);
-    if (cfg == 8 && n % 192 == 0) return launch_p8<3, ACT, HB, HR>(a, st);
-  }
-  if (cfg != 0 && k >= 256 && m >= 4096) {
-    if (cfg <= 2 && n % 256 == 0 && t256 * (n / 256) >= 512) {
-      const int tm = (int)t256, tn = n / 256;
-      if (cfg == 1) {
-        const size_t lds = std::max<size_t>(2 * (256 + 256) * 64 * 2, EPI_BIG_B);
-        gemm_bf16_tn_big<2, 4, 8, 4, 64, 2, ACT, HB, HR><<<dim3(tm * tn), dim3(512), lds, st>>>(x, w, b, r, y, m, n, k, tm, tn);
-      } else {
-        const size_t lds = std::max<size_t>(4 * (256 + 256) * 32 * 2, EPI_BIG_B);
-        gemm_bf16_tn_big<2, 4, 8, 4, 32, 4, ACT, HB, HR><<<dim3(tm * tn), dim3(512), lds, st>>>(x, w, b, r, y, m, n, k, tm, tn);
-      }
-      return;
+    case MMR_GEMM_ROUTE_P8_256X256:
+    case MMR_GEMM_ROUTE_P8_256X192: {
+      P8Args a;
+      a.x = x, a.w = w, a.bias = b, a.r = r, a.y = y, a.m = m, a.n = n, a.k = k;
+      a.ntst = p8_nt(m, n, 2);
+      if (cfg == 7) return launch_p8<4, ACT, HB, HR>(a, st);
+      return launch_p8<3, ACT, HB, HR>(a, st);
     }
-    if (cfg == 6 && n % 192 == 0 && t256 * (n / 192) >= 256) {
-      const int tm = (int)t256, tn = n / 192;
-      const size_t lds = std::max<size_t>(2 * (256 + 192) * 64 * 2, EPI_BIG_B);
-      gemm_bf16_tn_big<2, 4, 8, 3, 64, 2, ACT, HB, HR><<<dim3(tm * tn), dim3(512), lds, st>>>(x, w, b, r, y, m, n, k, tm, tn);
-      return;
-    }
-    if (cfg >= 4 && cfg <= 5 && n % 128 == 0) {  // 256x128, KB=32: 2 workgroups per CU (epilogue overlap)
-      const int tm = (int)t256, tn = n / 128;
-      if (cfg == 4) {
-        const size_t lds = std::max<size_t>(2 * (256 + 128) * 32 * 2, EPI_BIG_B);
-        gemm_bf16_tn_big<4, 2, 4, 4, 32, 2, ACT, HB, HR, 2><<<dim3(tm * tn), dim3(512), lds, st>>>(x, w, b, r, y, m, n, k, tm, tn);
-      } else {
-        const size_t lds = std::max<size_t>(3 * (256 + 128) * 32 * 2, EPI_BIG_B);
-        gemm_bf16_tn_big<4, 2, 4, 4, 32, 3, ACT, HB, HR, 2><<<dim3(tm * tn), dim3(512), lds, st>>>(x, w, b, r, y, m, n, k, tm, tn);
-      }
-      return;
-    }
-    if (n % 128 == 0 && t256 * (n / 128) >= 512) {
-      const int tm = (int)t256, tn = n / 128;
-      const size_t lds = std::max<size_t>(3 * (256 + 128) * 64 * 2, EPI_BIG_B);
-      gemm_bf16_tn_big<4, 2, 4, 4, 64, 3, ACT, HB, HR><<<dim3(tm * tn), dim3(512), lds, st>>>(x, w, b, r, y, m, n, k, tm, tn);
-      return;
+    case MMR_GEMM_ROUTE_BIG_256X256_KB64X2: return launch_big<2, 4, 8, 4, 64, 2, 1, ACT, HB, HR>(ba, st);
+    case MMR_GEMM_ROUTE_BIG_256X256_KB32X4: return launch_big<2, 4, 8, 4, 32, 4, 1, ACT, HB, HR>(ba, st);
+    case MMR_GEMM_ROUTE_BIG_256X192_KB64X2: return launch_big<2, 4, 8, 3, 64, 2, 1, ACT, HB, HR>(ba, st);
+    case MMR_GEMM_ROUTE_BIG_256X128_KB32X2: return launch_big<4, 2, 4, 4, 32, 2, 2, ACT, HB, HR>(ba, st);
+    case MMR_GEMM_ROUTE_BIG_256X128_KB32X3: return launch_big<4, 2, 4, 4, 32, 3, 2, ACT, HB, HR>(ba, st);
+    case MMR_GEMM_ROUTE_BIG_256X128_KB64X3: return launch_big<4, 2, 4, 4, 64, 3, 1, ACT, HB, HR>(ba, st);
+    default: {
+      const int bm = (int)mmr::ceil_div(m, BM), bn = (int)mmr::ceil_div(n, BN);
+      gemm_bf16_tn<ACT, HB, HR><<<dim3(bm * bn), dim3(256), 0, st>>>(x, w, b, r, y, m, n, k, bm, bn);
     }
   }
-  const int tm = (int)mmr::ceil_div(m, BM), tn = (int)mmr::ceil_div(n, BN);
-  gemm_bf16_tn<ACT, HB, HR><<<dim3(tm * tn), dim3(256), 0, st>>>(x, w, b, r, y, m, n, k, tm, tn);
 }
 
 // Per-shape variant choice: the first call with a (M, N, K, epilogue) key times every variant on
@@ -1973,6 +1992,12 @@ extern "C" int32_t mmr_linear_bf16_variant(int64_t m, int32_t n, int32_t k, int3
   std::lock_guard<std::mutex> lk(g_tune_mu);
   auto it = g_tuned.find(std::make_pair(dev, TuneKey{m, n, k, act, has_bias ? 1 : 0, has_residual ? 1 : 0}));
   return it == g_tuned.end() ? -1 : it->second;
+}
+
+extern "C" int32_t mmr_linear_bf16_route(int64_t m, int32_t n, int32_t k, int32_t has_residual, int32_t variant,
+                                         int32_t cus) {
+  if (m <= 0 || n <= 0 || k <= 0 || k % 8 != 0 || n % 8 != 0 || variant < 0 || variant >= kVariants) return -1;
+  return route(m, n, k, has_residual != 0, kVarW4[variant], kVarCfg[variant], cus > 0 ? cus : cu_count());
 }
 
 extern "C" mmr_status mmr_linear_bf16(const uint16_t* x, const uint16_t* w, const float* bias,

@@ -66,6 +66,19 @@ def linear(x, w, bias=None, residual=None, act=0, out=None):
     return y
 
 
+# mmr.h MMR_GEMM_ROUTE_*: the kernels mmr_linear_bf16 launches, by route id
+GEMM_ROUTES = ("base_128x128", "w4_256x256", "w4_256x192", "big_256x256_kb64x2", "big_256x256_kb32x4",
+               "big_256x192_kb64x2", "big_256x128_kb32x2", "big_256x128_kb32x3", "big_256x128_kb64x3", "p8_256x256",
+               "p8_256x192")
+
+
+def linear_route(m, n, k, has_residual=False, variant=0, cus=0):
+    """The route id (index into GEMM_ROUTES) mmr_linear_bf16 takes for an (m, n, k) GEMM under launch variant
+    `variant` on a device with `cus` compute units (0: the current device; an explicit count needs no GPU).
+    Launches nothing; -1 for arguments mmr_linear_bf16 refuses."""
+    return int(_L().mmr_linear_bf16_route(m, n, k, int(bool(has_residual)), variant, cus))
+
+
 class RWPack:
     """A weight image for mmr_linear_rw (resident-weight streaming linear): W (N, K) bf16 re-laid for
     LDS; `None` from rw_pack when the shape is not one the kernel takes."""
