@@ -889,6 +889,53 @@ mmr_status mmr_map_alignment(const float* maps, int64_t ld, int64_t n, int32_t h
                              double* pearson, double* spearman, int64_t* rank_sums, int64_t* inter_union,
                              int32_t* skipped, int64_t* nonfinite, void* work, void* stream);
 
+/* ---------------------------------------------------------------- gradient explanations */
+/* The backward kernels of the Grad-CAM / Integrated-Gradients maps (explain.py:170-427), csrc/explain_grad.hip: f32
+ * throughout, every sum in a fixed order, no floating-point atomics — a sequence's (row's, map's) result does not
+ * depend on what else is in the launch.
+ *
+ * Attention core, rows as mmr_x3_attention (q row bi*lq + i at q + row*ldq + head*dh; one ld per operand).
+ * mmr_attention_fwd_f32: out = softmax(scale q k^T) v with every contraction on the f32-input MFMA (exp by ocml
+ * expf): the forward the gradient pass differentiates.  mmr_attention_bwd_f32: given d_out = dL/dout, per
+ * (sequence, head) S = scale q k^T and P = softmax(S) are recomputed (no probabilities are saved), then
+ *   dV = P^T dO;  dP = dO V^T;  dS = P o (dP - rowsum(dP o P));  dQ = scale dS K;  dK = scale dS^T Q.
+ * dq / dk / dv may each be NULL: that output is not computed (all NULL: no launch).  Columns [heads*dh, ld) of the
+ * output rows are not written.
+ * Limits: 1 <= lq, lk <= 128; dh % 8 == 0, 8 <= dh <= 96 — anything else MMR_ERR_UNSUPPORTED (nothing is clamped);
+ * q, k, v, d_out 16-B aligned with row strides that are multiples of 4 and >= heads*dh, output strides >= heads*dh,
+ * no NULL input (MMR_ERR_INVALID).  b == 0: no launch. */
+mmr_status mmr_attention_fwd_f32(const float* q, int64_t ldq, const float* k, int64_t ldk, const float* v, int64_t ldv,
+                                 float* out, int64_t ldo, int32_t b, int32_t lq, int32_t lk, int32_t heads, int32_t dh,
+                                 float scale, void* stream);
+mmr_status mmr_attention_bwd_f32(const float* q, int64_t ldq, const float* k, int64_t ldk, const float* v, int64_t ldv,
+                                 const float* d_out, int64_t ldo, float* dq, int64_t lddq, float* dk, int64_t lddk,
+                                 float* dv, int64_t lddv, int32_t b, int32_t lq, int32_t lk, int32_t heads, int32_t dh,
+                                 float scale, void* stream);
+/* LayerNorm backward over strided rows: for y = LN(z) gamma + beta, given the saved pre-norm row z and dy,
+ * dz = rstd (g^ - mean(g^) - z^ mean(g^ o z^)) with g^ = gamma o dy, z^ = (z - mean z) rstd, rstd = 1 / sqrt(var z +
+ * eps) (two-pass variance).  1 <= c <= 1024.  One parameter set (no groups). */
+mmr_status mmr_ln_bwd_rows(const float* z, int64_t ldz, const float* gamma, const float* dy, int64_t lddy, float* dz,
+                           int64_t lddz, int64_t rows, int32_t c, float eps, void* stream);
+/* GELU (the exact erf form, ocml erff) over strided rows of the pre-activation h: dx = dy (Phi(h) + h phi(h)) (dx
+ * NULL: not computed; else dy is required) and / or y = h Phi(h) (y NULL: not computed). */
+mmr_status mmr_gelu_bwd_rows(const float* h, int64_t ldh, const float* dy, int64_t lddy, float* dx, int64_t lddx,
+                             float* y, int64_t ldy, int64_t rows, int32_t c, void* stream);
+/* Attribution vectors and maps.  grad (maps*steps, np, ci) contiguous: the rows of map m are m*steps + s; x (.., np,
+ * ci) contiguous: map m reads x[(m / x_div) % x_mod] (maps ordered (sample, target): x_div = targets, x_mod = samples;
+ * ordered (target, sample): x_div = 1, x_mod = samples); step_w (steps) the quadrature weights, NULL = 1.
+ * t_e = (sum_s step_w[s] grad[m*steps + s, j, e]) x[.., j, e], steps summed in order; the step and channel sums
+ * run in f64 in a fixed order and are rounded to f32 once.
+ *   mode 0, Grad-CAM (explain.py:274-300): raw[m, j] = sum_e t_e (BEFORE the relu); map = relu, G x G, bilinear
+ *     (align_corners=False) to (h, w), THEN (v - min) / ((max - min) + 1e-8f) over the pixels, then nan_to_num(0, 1, 0)
+ *   mode 1, Integrated Gradients (:403-427): raw[m, j] = sum_e |t_e|; map = (a - min) / ((max - min) + 1e-8f) over
+ *     the patches, clamp to [0, 1], nan_to_num(0, 1, 0), THEN bilinear to (h, w)
+ * raw (maps, np) is always written; out_maps (maps, h, w) may be NULL (then np need not be a square).
+ * MMR_ERR_INVALID: np outside 1..1024 or not a perfect square with out_maps; h*w outside 1..65536; steps outside
+ * 1..1024. */
+mmr_status mmr_attribution_maps(const float* grad, const float* x, const float* step_w, int64_t maps, int32_t steps,
+                                int32_t x_div, int32_t x_mod, int32_t np, int32_t ci, int32_t mode, int32_t h, int32_t w,
+                                float* raw, float* out_maps, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -22,6 +22,7 @@
 // upscale_heatmap to the same size is the identity and is not run.)  4 consecutive pixels per thread, one 16-B store
 // — where H W is a multiple of 4, so that every sample's map starts 16-B aligned (224 x 224, 28 x 28, ...); any other
 // H W takes scalar stores for the whole map.
+#include "bilinear.h"
 #include "common.h"
 
 #pragma clang fp contract(off)
@@ -296,15 +297,6 @@ struct ExHeat {
   float sh, sw;  // (float)G / H, (float)G / W
 };
 
-__device__ __forceinline__ void ex_src(int d, float scale, int g, int& i0, int& i1, float& l1) {
-  float s = ((float)d + 0.5f) * scale - 0.5f;
-  s = s < 0.0f ? 0.0f : s;
-  i0 = (int)s;
-  i0 = i0 < g - 1 ? i0 : g - 1;
-  i1 = i0 < g - 1 ? i0 + 1 : i0;
-  l1 = s - (float)i0;
-}
-
 __global__ __launch_bounds__(256) void ex_heat(const ExHeat a) {
   __shared__ ExSm sm;
   __shared__ float v[EX_MAXNP];
@@ -327,12 +319,7 @@ __global__ __launch_bounds__(256) void ex_heat(const ExHeat a) {
     for (int j = 0; j < 4; ++j) {
       const int p = p0 + j < hw ? p0 + j : hw - 1;
       const int y = p / a.w, x = p - y * a.w;
-      int y0, y1, x0, x1;
-      float ly, lx;
-      ex_src(y, a.sh, g, y0, y1, ly);
-      ex_src(x, a.sw, g, x0, x1, lx);
-      const float hy = 1.0f - ly, hx = 1.0f - lx;
-      o[j] = hy * (hx * v[y0 * g + x0] + lx * v[y0 * g + x1]) + ly * (hx * v[y1 * g + x0] + lx * v[y1 * g + x1]);
+      o[j] = mmr::bilinear_at(v, g, y, x, a.sh, a.sw);
     }
     if (vec) {
       *reinterpret_cast<float4*>(dst + p0) = make_float4(o[0], o[1], o[2], o[3]);

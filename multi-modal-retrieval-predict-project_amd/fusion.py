@@ -125,6 +125,10 @@ class FusionStack:
         self.x3 = x3
         n = 1 + max(int(k.split(".")[1]) for k in sd if k.startswith("fusion_layers."))
         self.layers = []
+        # the last layer's weights as given (references, no copies): explain_grad.GradientExplainer builds its f32
+        # copies from them on first use
+        last = f"fusion_layers.{n - 1}."
+        self.last_layer_state = {k[len(last):]: v for k, v in sd.items() if k.startswith(last)}
         D = sd["self_attn.in_proj_weight"].shape[1]
         self.D = D
         for i in range(n):

@@ -305,9 +305,11 @@ class MultiModalRetrievalModel:
         self.num_fusion_layers = num_fusion_layers
         # model.py:271-277 classifier: Linear(D, 4D), GELU, Dropout, Linear(4D, C), Dropout (eval: identities)
         self.classifier = None
+        self._classifier_f32 = self._grad_explainer = None
         if "classifier.0.weight" in hs:
-            self.classifier = ops.ClassifierW(f("classifier.0.weight"), f("classifier.0.bias"),
-                                              f("classifier.3.weight"), f("classifier.3.bias"))
+            cls_w = (f("classifier.0.weight"), f("classifier.0.bias"), f("classifier.3.weight"), f("classifier.3.bias"))
+            self.classifier = ops.ClassifierW(*cls_w)
+            self._classifier_f32 = cls_w  # explain_gradients differentiates the f32 head (ClassifierW keeps images only)
             if self.classifier.d != joint_dim:
                 raise ValueError(f"classifier.0.weight takes {self.classifier.d} inputs, joint_dim is {joint_dim}")
             self.num_classes = self.classifier.c  # the weights decide, as for num_fusion_layers
@@ -385,15 +387,19 @@ class MultiModalRetrievalModel:
         attention dictionary for query 0 (explain.py:825-947) as numpy float32 from explain_attention, keys in the
         reference's order and left out / None where it does so: "txt2img" (H, W), "img2txt" (Lt,), "comb_img"
         (H, W; left out when the vector is all zeros), "comb_txt", "final_patch_map", "final_token_map" — and
-        "ig_maps": None, "gradcam_maps": None.  explain=True — the reference's Integrated-Gradients / Grad-CAM
-        maps — is not part of this inference-only package."""
-        attention = isinstance(explain, str) and explain == "attention"
+        "ig_maps": None, "gradcam_maps": None.  explain="full": the same dictionary with the reference's
+        explain=True maps for query 0: "ig_maps" / "gradcam_maps" = {t: (H, W) np.float32} over topk_idx[0]
+        (explain_gradients with samples=[0]; the reference's n_steps = 50 and 224 x 224).  explain=True itself still
+        raises: switching it over to explain="full" is a later change."""
+        full = isinstance(explain, str) and explain == "full"
+        attention = full or (isinstance(explain, str) and explain == "attention")
         if explain and not attention:
             raise NotImplementedError(
                 "predict(explain=True): the reference's IG / Grad-CAM explanations need autograd and Captum and are "
                 "out of scope here; use predict(..., explain=\"attention\") for the attention heat maps "
                 "(explain_attention for whole batches), forward(..., return_attention=True) for the raw maps and "
-                "predict(..., retrieve=True) for the retrieved neighbours")
+                "predict(..., retrieve=True) for the retrieved neighbours; predict(..., explain=\"full\") adds the "
+                "Grad-CAM / Integrated-Gradients maps computed on the device (explain_gradients)")
         if self.classifier is None:
             raise ValueError("predict needs classifier.0.* / classifier.3.* weights in the checkpoint / head_state")
         if (retrieve or attention) and self.retriever is None:
@@ -441,7 +447,84 @@ class MultiModalRetrievalModel:
             amap["final_patch_map"] = first("final_patch_map")
             amap["final_token_map"] = first("final_token_map")
             output.update({"attention_map": amap, "ig_maps": None, "gradcam_maps": None})
+        if full:
+            top0 = [int(t) for t in output["topk_idx"][0]]
+            g = self.explain_gradients(image, input_ids, attention_mask, targets=top0, samples=[0])
+            for key, name in (("ig_maps", "ig_maps"), ("gradcam_maps", "gradcam_maps")):
+                m = g[name][0].cpu().numpy()
+                output[key] = {t: m[i] for i, t in enumerate(top0)}
         return output
+
+    def explain_gradients(self, image, input_ids, attention_mask, targets=None, K=5, methods=("gradcam", "ig"),
+                          ig_steps=50, image_size=(224, 224), *, samples=None):
+        """The gradient family of ExplanationEngine (explain.py:170-427: compute_gradcam_map_for_target and
+        compute_ig_map_for_target, multimodal form) for every sample of the batch, on the device without autograd
+        (explain_grad.GradientExplainer: the last fusion layer and the classifier in f32 on the towers' features,
+        whatever tower_dtype is).  The reference applies the classifier to every token of the fused sequence, so a
+        target t selects the TOKEN t of [x1; patches_fused; x2]: Grad-CAM scores sum_c logits[t, c] with img_global
+        constant, IG scores logits[t, t] with img_global = mean_j P_j, baseline 0 and Captum's default Gauss-Legendre
+        rule with ig_steps nodes (alpha_s = (1 + x_s) / 2, w_s = omega_s / 2 for leggauss; the reference always runs
+        its method default n_steps = 50).  targets: None (each sample's own top-K classes, in classifier_head's
+        order), a list shared by all samples, or a (B, T) tensor.  -> device tensors "targets" (B, T) int64,
+        "gradcam_maps" / "ig_maps" (B, T, H, W) f32, "gradcam_raw" (B, T, Np) = sum_e dS/dP P before the relu,
+        "ig_raw" (B, T, Np) = sum_e |A|, "token_logits" (B, Np + 2, C) (the entries of a method not in `methods` are
+        None).  input_ids=None: the default text token.  samples: the batch indices to explain (default all; the
+        towers still run on the whole batch, so a sample's maps are the same bytes either way).
+        ValueError: a model that is not multimodal or has no classifier, Np not a perfect square (IG asserts it,
+        :402), a target outside [0, Np + 2) or, with IG, outside [0, C) (the reference raises IndexError).
+        Out of scope: the unimodal maps (random projections in the reference), other layers, token attributions,
+        overlays."""
+        if self.model_type != "multimodal":
+            raise ValueError(f"explain_gradients needs model_type='multimodal', not {self.model_type!r}")
+        if self.classifier is None:
+            raise ValueError("explain_gradients needs classifier.0.* / classifier.3.* weights")
+        if image is None:
+            raise ValueError("model_type='multimodal' needs an image (fusion.py:421)")
+        methods = tuple(methods)
+        if not methods or any(m not in ("gradcam", "ig") for m in methods):
+            raise ValueError(f"explain_gradients: methods {methods!r} (out of 'gradcam', 'ig')")
+        img_global, patches, _ = self.backbones.encode_image(image, want_patches=True)
+        txt = self.backbones.encode_text(input_ids, attention_mask) if input_ids is not None else None
+        B, npatch, _ = patches.shape
+        if math.isqrt(npatch) ** 2 != npatch:
+            raise ValueError(f"explain_gradients: the patch count {npatch} is not a perfect square (explain.py:402)")
+        C = self.classifier.c
+        if targets is None:
+            joint = self.fusion.forward(img_global, patches, txt)
+            tg = ops.classifier_head(joint, self.classifier, k=K, want=("topk_idx",))["topk_idx"].to(torch.int64)
+        else:
+            tg = torch.as_tensor(targets).to(device=self.device, dtype=torch.int64)
+            if tg.dim() == 1:
+                tg = tg[None, :].expand(B, -1)
+            if tg.dim() != 2 or tg.shape[0] != B or tg.shape[1] < 1:
+                raise ValueError(f"explain_gradients: targets must be a list or (B, T), got {tuple(tg.shape)}")
+        lo, hi = int(tg.min()), int(tg.max())
+        limit = min(npatch + 2, C) if "ig" in methods else npatch + 2
+        if lo < 0 or hi >= limit:
+            raise ValueError(f"explain_gradients: targets span [{lo}, {hi}], outside [0, {limit}) (tokens: {npatch + 2}"
+                             f"{', classes: ' + str(C) if 'ig' in methods else ''})")
+        if self._grad_explainer is None:
+            from .explain_grad import GradientExplainer
+            self._grad_explainer = GradientExplainer(self.fusion.last_layer_state, self._classifier_f32, self.num_heads,
+                                                     self.device, eps=self.fusion.eps)
+        ex = self._grad_explainer
+        P, G = patches.float().contiguous(), img_global.float().contiguous()
+        T32 = txt.float() if txt is not None else ex.W["default_txt"].expand(B, -1, -1)
+        tg = tg.contiguous()
+        if samples is not None:
+            idx = torch.as_tensor(list(samples), dtype=torch.int64, device=self.device)
+            P, G, T32, tg = P[idx].contiguous(), G[idx].contiguous(), T32[idx], tg[idx].contiguous()
+        TQ, tproj = ex.text_side(T32.contiguous())
+        out = {"targets": tg, "gradcam_maps": None, "gradcam_raw": None, "ig_maps": None, "ig_raw": None,
+               "token_logits": None}
+        if "gradcam" in methods:
+            _, out["gradcam_raw"], out["gradcam_maps"], out["token_logits"] = ex.gradcam(G, P, TQ, tproj, tg, image_size)
+        else:
+            S = ex.forward_sets(P, G, TQ, tproj, 1)
+            out["token_logits"] = ex.token_logits(S["seq"])
+        if "ig" in methods:
+            out["ig_raw"], out["ig_maps"] = ex.integrated_gradients(P, TQ, tproj, tg, ig_steps, image_size)
+        return out
 
     def explain_attention(self, image, input_ids, attention_mask, layer=-1, image_size=(224, 224)):
         """The attention family of ExplanationEngine.explain (explain.py:825-947) for every sample of the batch

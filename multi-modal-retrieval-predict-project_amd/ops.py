@@ -1336,3 +1336,126 @@ def x3_gather_rows(x, b, c, ldx, out=None):
     y = out if out is not None else torch.empty((b, c), dtype=torch.float32, device=x.device)
     _chk(_L().mmr_x3_gather_rows(_lib.ptr(x), ldx, _lib.ptr(y), b, c, _s(x)), "mmr_x3_gather_rows")
     return y
+
+
+# ---- gradient explanations (csrc/explain_grad.hip) ----
+ATTENTION_BWD_MAX_LEN, ATTENTION_BWD_MAX_DH = 128, 96
+
+
+def _rows2(t, name):
+    if t.dim() != 2 or t.dtype != torch.float32 or t.stride(1) != 1:
+        raise ValueError(f"{name} must be a 2-D float32 row view with unit column stride, got {tuple(t.shape)} {t.dtype}")
+    return t
+
+
+def attention_fwd(q, k, v, b, lq, lk, heads, dh, scale, out=None):
+    """softmax(scale q k^T) v per (sequence, head) on the f32-input MFMA (mmr_attention_fwd_f32): q (b*lq, >=
+    heads*dh), k / v (b*lk, ..) f32 row views (column slices of a packed tensor are fine) -> out (b*lq, heads*dh)."""
+    _lib.require_gpu(q)
+    for t, n in ((q, "q"), (k, "k"), (v, "v")):
+        _rows2(t, n)
+    y = out if out is not None else torch.empty((b * lq, heads * dh), dtype=torch.float32, device=q.device)
+    _chk(_L().mmr_attention_fwd_f32(_lib.ptr(q), q.stride(0), _lib.ptr(k), k.stride(0), _lib.ptr(v), v.stride(0),
+                                    _lib.ptr(y), y.stride(0), b, lq, lk, heads, dh, float(scale), _s(q)),
+         "mmr_attention_fwd_f32")
+    return y
+
+
+def attention_bwd(q, k, v, d_out, b, lq, lk, heads, dh, scale, want=("dq", "dk", "dv"), out=None):
+    """Backward of the attention core (mmr_attention_bwd_f32): q, k, v as attention_fwd, d_out (b*lq, >= heads*dh)
+    -> (dq, dk, dv), None for the ones not in `want` (not computed).  out: a dict of preallocated row views by name.
+    1 <= lq, lk <= 128, dh % 8 == 0, dh <= 96; f32, fixed-order sums, no atomics."""
+    _lib.require_gpu(q)
+    for t, n in ((q, "q"), (k, "k"), (v, "v"), (d_out, "d_out")):
+        _rows2(t, n)
+    res = {}
+    for name, rows in (("dq", b * lq), ("dk", b * lk), ("dv", b * lk)):
+        if name not in want:
+            res[name] = None
+        elif out is not None and out.get(name) is not None:
+            res[name] = _rows2(out[name], name)
+        else:
+            res[name] = torch.empty((rows, heads * dh), dtype=torch.float32, device=q.device)
+
+    def ld(t):
+        return t.stride(0) if t is not None else 0
+    _chk(_L().mmr_attention_bwd_f32(_lib.ptr(q), q.stride(0), _lib.ptr(k), k.stride(0), _lib.ptr(v), v.stride(0),
+                                    _lib.ptr(d_out), d_out.stride(0), _lib.ptr(res["dq"]), ld(res["dq"]),
+                                    _lib.ptr(res["dk"]), ld(res["dk"]), _lib.ptr(res["dv"]), ld(res["dv"]), b, lq, lk,
+                                    heads, dh, float(scale), _s(q)), "mmr_attention_bwd_f32")
+    return res["dq"], res["dk"], res["dv"]
+
+
+def ln_bwd_rows(z, g, dy, eps, out=None):
+    """dz of y = LN(z) g + b over 2-D f32 row views (mmr_ln_bwd_rows): z the saved pre-norm rows, dy = dL/dy."""
+    _lib.require_gpu(z)
+    _rows2(z, "z"), _rows2(dy, "dy")
+    rows, c = z.shape
+    if tuple(dy.shape) != (rows, c) or g.numel() != c:
+        raise ValueError(f"ln_bwd_rows: z {tuple(z.shape)}, dy {tuple(dy.shape)}, gamma {tuple(g.shape)}")
+    dz = out if out is not None else torch.empty((rows, c), dtype=torch.float32, device=z.device)
+    _chk(_L().mmr_ln_bwd_rows(_lib.ptr(z), z.stride(0), _lib.ptr(g), _lib.ptr(dy), dy.stride(0), _lib.ptr(dz),
+                              dz.stride(0), rows, c, float(eps), _s(z)), "mmr_ln_bwd_rows")
+    return dz
+
+
+def gelu_bwd(h, dy, out=None):
+    """dy * gelu'(h), the exact erf form, over 2-D f32 row views (mmr_gelu_bwd_rows)."""
+    _lib.require_gpu(h)
+    _rows2(h, "h"), _rows2(dy, "dy")
+    if dy.shape != h.shape:
+        raise ValueError(f"gelu_bwd: h {tuple(h.shape)}, dy {tuple(dy.shape)}")
+    rows, c = h.shape
+    dx = out if out is not None else torch.empty((rows, c), dtype=torch.float32, device=h.device)
+    _chk(_L().mmr_gelu_bwd_rows(_lib.ptr(h), h.stride(0), _lib.ptr(dy), dy.stride(0), _lib.ptr(dx), dx.stride(0), None,
+                                0, rows, c, _s(h)), "mmr_gelu_bwd_rows")
+    return dx
+
+
+def gelu_rows(h):
+    """gelu(h) with the same erff as gelu_bwd (mmr_gelu_bwd_rows' forward output)."""
+    _lib.require_gpu(h)
+    _rows2(h, "h")
+    rows, c = h.shape
+    y = torch.empty((rows, c), dtype=torch.float32, device=h.device)
+    _chk(_L().mmr_gelu_bwd_rows(_lib.ptr(h), h.stride(0), None, 0, None, 0, _lib.ptr(y), y.stride(0), rows, c, _s(h)),
+         "mmr_gelu_bwd_rows")
+    return y
+
+
+def attribution_maps(grad, x, mode, steps=1, step_w=None, image_size=None, target_major=False):
+    """Per-patch attribution vectors and (H, W) maps (mmr_attribution_maps).  grad (maps*steps, Np, Ci) f32: map m's
+    rows are m*steps + s; x (X, Np, Ci): the maps are ordered (patch set, target) — map m reads x[m // (maps // X)] —
+    or, target_major, (target, patch set) — x[m % X]; step_w (steps,) quadrature weights or None.
+    mode "gradcam": raw = sum_e g x (before the relu), map = relu -> bilinear -> min-max over the pixels; mode "ig":
+    raw = sum_e |sum_s w_s g_s x|, map = min-max over the patches, clamp -> bilinear.  -> (raw (maps, Np), maps
+    (maps, H, W) or None without image_size)."""
+    _lib.require_gpu(grad)
+    if mode not in ("gradcam", "ig"):
+        raise ValueError(f"attribution_maps: mode {mode!r}")
+    if grad.dim() != 3 or x.dim() != 3 or grad.dtype != torch.float32 or x.dtype != torch.float32:
+        raise ValueError("attribution_maps: grad and x must be 3-D float32")
+    grad, x = grad.contiguous(), x.contiguous()
+    R, npp, ci = (int(s) for s in grad.shape)
+    steps = int(steps)
+    if steps < 1 or R % steps or tuple(x.shape[1:]) != (npp, ci):
+        raise ValueError(f"attribution_maps: grad {tuple(grad.shape)}, x {tuple(x.shape)}, steps {steps}")
+    maps = R // steps
+    X = int(x.shape[0])
+    if X < 1 or maps % X:
+        raise ValueError(f"attribution_maps: {maps} maps over {X} patch sets")
+    if step_w is not None:
+        step_w = step_w.to(device=grad.device, dtype=torch.float32).contiguous()
+        if step_w.numel() != steps:
+            raise ValueError(f"attribution_maps: {step_w.numel()} weights for {steps} steps")
+    raw = torch.empty((maps, npp), dtype=torch.float32, device=grad.device)
+    out = None
+    H = W = 0
+    if image_size is not None:
+        H, W = int(image_size[0]), int(image_size[1])
+        out = torch.empty((maps, H, W), dtype=torch.float32, device=grad.device)
+    _chk(_L().mmr_attribution_maps(_lib.ptr(grad), _lib.ptr(x), _lib.ptr(step_w), maps, steps,
+                                   1 if target_major else max(maps // X, 1), X, npp, ci, int(mode == "ig"), H, W,
+                                   _lib.ptr(raw), _lib.ptr(out), _s(grad)),
+         "mmr_attribution_maps")
+    return raw, out
